@@ -12,8 +12,13 @@ scaling, default) or --total-rows T split into contiguous shards (strong scaling
 
 Prints ONE JSON line (rank 0).  `value` = total algorithmic bytes of all ranks / max-over-ranks
 time (encode reads 800 B + writes 816 B per row, decode the reverse; 3,232 B/row).
-Also reports the dominant kernel's roofline (HIP events on the launch stream) and the CPU
-baseline (oracle C restatement of the Java writer/reader, 1 thread, bounded sample).
+A plain run sets up, warms up, times the steps and prints the line; its `roofline` holds the
+encode / decode split of the timed steps (HIP events on the launch stream).  --dump-outputs DIR
+also writes what the last timed step computed as .npy files (same arguments: same inputs, so
+two builds compare output for output).  --full adds everything that takes runs of its own: the
+achievable copy rate and PMC traffic in `roofline`, the post-timing correctness spot check, the
+host-memory round trip and the CPU baseline (oracle C restatement of the Java writer/reader,
+1 thread and the job's CPU share, bounded sample).
 """
 from __future__ import annotations
 
@@ -54,13 +59,21 @@ def _parse(argv=None):
     p.add_argument("--share-gpus", action="store_true",
                    help="rehearsal only: allow more ranks than visible GPUs (ranks share them)")
     p.add_argument("--workload", default="struct100", choices=["struct100", "mixed", "nested"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: the achievable HBM copy rate and PMC traffic "
+                        "in `roofline`, the post-timing correctness spot check, the host-memory "
+                        "(PCIe) round trip `e2e_pcie` and the `cpu_baseline`")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed (rows, row "
+                        "offsets, decoded columns) as DIR/<name>.npy, see dump_outputs")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--cpu-rows", type=int, default=None,
                    help="rows of the CPU baseline's batch (default: the bench batch, C2 = 1M)")
-    p.add_argument("--no-e2e", action="store_true")
+    p.add_argument("--no-e2e", action="store_true", help="with --full: no e2e_pcie")
     p.add_argument("--no-verify", action="store_true",
-                   help="diagnostic runs only: skip the post-timing correctness spot check")
+                   help="with --full, diagnostic runs only: skip the post-timing correctness "
+                        "spot check")
     a = p.parse_args(argv)
     if a.rows is None:
         a.rows = DEFAULT_ROWS[a.workload]
@@ -85,6 +98,97 @@ def make_device_columns(name, fields, rows, start, dev):
     generator, tests/test_workloads.py)."""
     from fury_amd.workloads import gen_columns_torch
     return gen_columns_torch(name, fields, rows, seed=1234, start=start, device=dev)
+
+
+DUMP_BUDGET = 48 << 20     # bytes of .npy payload, all ranks together (--dump-outputs; limit 64 MB)
+DUMP_SEED = 20240607
+DUMP_CHUNK = 64            # elements per sampled run
+
+
+def _bitmap(t, m):
+    """The (m + 7) // 8 bytes of an m-entry bitmap, bits past m cleared (buffers are padded)."""
+    nb = (m + 7) // 8
+    t = t.view(-1)[:nb].clone()
+    if m % 8:
+        t[-1] &= (1 << (m % 8)) - 1
+    return t
+
+
+def _column_outputs(f, c, m, name, out):
+    """Appends (name, 1-D tensor) for every buffer of column `c` (m entries of field `f`), cut to
+    the bytes the decode defines: capacity padding past them is uninitialised."""
+    import torch
+    from fury_amd.types import BOOL, DECIMAL, LIST, STRING, BINARY, STRUCT, type_width
+    if c.validity is not None:
+        out.append((name + ".validity", _bitmap(c.validity, m)))
+    t = f.type_id
+    if t == BOOL:
+        out.append((name + ".values", _bitmap(c.values, m)))
+    elif t in (STRING, BINARY):
+        out.append((name + ".offsets", c.offsets.view(-1)[:m + 1]))
+        out.append((name + ".values", c.values.view(-1)[:int(c.offsets[m].item()) if m else 0]))
+    elif t == LIST:
+        out.append((name + ".offsets", c.offsets.view(-1)[:m + 1]))
+        _column_outputs(f.children[0], c.child[0], int(c.offsets[m].item()) if m else 0,
+                        name + "." + f.children[0].name, out)
+    elif t == STRUCT:
+        for g, d in zip(f.children, c.child):
+            _column_outputs(g, d, m, name + "." + g.name, out)
+    elif t == DECIMAL or type_width(t) > 0:
+        w = 16 if t == DECIMAL else type_width(t)
+        out.append((name + ".values", c.values.view(torch.uint8).view(-1)[:m * w]))
+    else:
+        raise SystemExit(f"bench.py: --dump-outputs does not know field {f}")
+
+
+def _blocksums(t, block):
+    """int64 sums of t[i] * (1 + i % block % 251) over consecutive blocks of `block` elements."""
+    import torch
+    weight = (torch.arange(block, device=t.device) % 251 + 1).to(torch.int64)
+    sums = []
+    step = max(1, (32 << 20) // block)            # blocks per pass: 32M elements at a time
+    for b in range(0, -(-t.numel() // block), step):
+        part = t[b * block:(b + step) * block].to(torch.int64)
+        pad = -part.numel() % block
+        if pad:
+            part = torch.cat([part, part.new_zeros(pad)])
+        sums.append((part.view(-1, block) * weight).sum(1))
+    return torch.cat(sums)
+
+
+def dump_outputs(dirname, named, prefix="", budget=None):
+    """Writes the timed path's outputs as DIR/<name>.npy: byte buffers as float32 (one element per
+    byte), int32 / int64 offsets as float64, both exact.  When everything fits `budget` (this
+    rank's part of DUMP_BUDGET) the arrays are whole.  Otherwise each buffer gets a share of the
+    budget in proportion to its size, half of it for <name>.npy = a seeded sample (sorted runs of
+    DUMP_CHUNK consecutive elements; the run indices depend only on DUMP_SEED, the name's
+    position and the buffer's length, so two builds sample the same elements) and half for
+    <name>.blocksum.npy = float64 sums of element * (1 + index in block % 251) over consecutive
+    blocks that cover the whole buffer."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    cost = [t.numel() * (4 if t.dtype == torch.uint8 else 8) for _, t in named]
+    scale = min(1.0, (budget or DUMP_BUDGET) / max(sum(cost), 1))
+    for k, (name, t) in enumerate(named):
+        path = os.path.join(dirname, prefix + name)
+        ft = torch.float32 if t.dtype == torch.uint8 else torch.float64
+        per = 4 if t.dtype == torch.uint8 else 8
+        share = int(cost[k] * scale)
+        if scale >= 1.0 or t.numel() <= 4 * DUMP_CHUNK:
+            np.save(path + ".npy", t.to(ft).cpu().numpy())
+            continue
+        runs = -(-t.numel() // DUMP_CHUNK)
+        want = max(1, share // 2 // per // DUMP_CHUNK)
+        rng = np.random.default_rng([DUMP_SEED, k, t.numel()])
+        pick = np.unique(rng.integers(0, runs, size=want))
+        idx = torch.from_numpy(pick).to(t.device)[:, None] * DUMP_CHUNK \
+            + torch.arange(DUMP_CHUNK, device=t.device)[None, :]
+        inside = idx < t.numel()
+        sample = torch.where(inside, t[idx.clamp_(max=t.numel() - 1)], torch.zeros_like(t[:1]))
+        np.save(path + ".npy", sample.view(-1).to(ft).cpu().numpy())
+        block = -(-t.numel() // max(1, share // 2 // 8))
+        np.save(path + ".blocksum.npy", _blocksums(t, block).to(torch.float64).cpu().numpy())
 
 
 def _host_cpus():
@@ -248,8 +352,9 @@ def run(args):
             ev[2].record(stream)
 
     # the box's achievable streaming copy, same device, same stream, before the timed loop
-    # (VERDICT r5 item 6): separates a slow box from a slow kernel in the roofline line
-    copy = copy_rate(dev, stream)
+    # (VERDICT r5 item 6): separates a slow box from a slow kernel in the roofline line; a run of
+    # its own, so --full only
+    copy = copy_rate(dev, stream) if args.full else None
 
     for _ in range(args.warmup):
         step()
@@ -268,8 +373,18 @@ def run(args):
 
     dt_max = orch.max(dt)
 
+    if args.dump_outputs:
+        named = [("rows", batch.rows)]
+        if offs is not None:
+            named.append(("row_offsets", offs.view(-1)[:n + 1]))
+        for f, c in zip(fields, out_cols if out_cols is not None else var_out):
+            _column_outputs(f, c, n, f.name, named)
+        dump_outputs(args.dump_outputs, named, prefix="" if world == 1 else f"rank{rank}.",
+                     budget=DUMP_BUDGET // world)
+        del named
+
     # correctness spot check after timing (cheap, device-side): decoded == input
-    if args.no_verify:
+    if args.no_verify or not args.full:
         pass
     elif args.workload == "struct100":
         for c, d in zip(cols[:4], out_cols[:4]):
@@ -284,9 +399,11 @@ def run(args):
                 assert torch.equal(c.offsets, d.offsets), "decode offsets mismatch"
 
     e2e = None
-    if world == 1 and not args.no_e2e and args.workload == "struct100":
+    if not args.full or world != 1 or args.no_e2e:
+        pass
+    elif args.workload == "struct100":
         e2e = end_to_end(enc, cols, n, dev, stream)
-    elif world == 1 and not args.no_e2e:
+    else:
         e2e = end_to_end_var(enc, cols, n, int(offs[n].item()))
 
     # every rank's bytes and rows (shards may differ by one row under strong scaling)
@@ -301,7 +418,7 @@ def run(args):
     traffic = None
     # PMC traffic (scripts/pmc.sh, scripts/pmc_var_traffic.sh) applies to the same workload and size
     pmc_file = os.path.join(ROOT, "profiles", f"pmc_{args.workload}.json")
-    if os.path.exists(pmc_file) and n == DEFAULT_ROWS[args.workload]:
+    if args.full and os.path.exists(pmc_file) and n == DEFAULT_ROWS[args.workload]:
         pm = json.load(open(pmc_file))
         traffic = pm.get(f"{dominant[0]}_hbm_bytes_per_launch")
     data = "synthetic SplitMix64 columns keyed by (column, global row) generated in HBM; no dataset"
@@ -330,6 +447,7 @@ def run(args):
         "shared_gpus": shared,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(dt_max * 1e3 / args.steps, 4),
         "higher_is_better": True,
         "scaling": scaling,
@@ -346,17 +464,17 @@ def run(args):
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "encode_ms": round(enc_ms, 4), "decode_ms": round(dec_ms, 4),
                      "encode_GBps": round(enc_bytes / (enc_ms * 1e-3) / 1e9, 1),
-                     "decode_GBps": round(dec_bytes / (dec_ms * 1e-3) / 1e9, 1),
-                     "copy_GBps": copy["GBps"],
-                     "frac_of_copy": round(achieved / copy["GBps"], 4),
-                     "copy": copy["what"]},
+                     "decode_GBps": round(dec_bytes / (dec_ms * 1e-3) / 1e9, 1)},
     }
+    if copy is not None:
+        line["roofline"].update(copy_GBps=copy["GBps"],
+                                frac_of_copy=round(achieved / copy["GBps"], 4), copy=copy["what"])
     if shared:
         line["rehearsal"] = (f"{world} ranks shared {min(world, ndev)} GPU(s) (--share-gpus): a "
                              "check of the multi-rank path, not a multi-GPU measurement")
     if e2e is not None:
         line["e2e_pcie"] = e2e
-    if world == 1 and not args.no_cpu_baseline:     # the CPU baseline is an N=1 figure
+    if args.full and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is an N=1 figure
         line["cpu_baseline"] = cpu_baseline(args.workload, fields, args.cpu_seconds,
                                             args.cpu_rows or min(n, 1_000_000))
     print(json.dumps(line), flush=True)

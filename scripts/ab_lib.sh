@@ -13,7 +13,7 @@ for rep in 1 2 3; do
   for w in $WL; do
     for lib in new old; do
       if [ $lib = old ]; then export FURY_ROW_LIB=$PWD/fury_amd/libfury_row_$TAG.so; else unset FURY_ROW_LIB; fi
-      timeout -k 10 240 python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-e2e > gpurun_out/ab_one.json 2> gpurun_out/ab_one.err
+      timeout -k 10 240 python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-e2e > ${OUT%/*}/ab_one.json 2> ${OUT%/*}/ab_one.err
       rc=$?
       if [ $rc -ne 0 ]; then echo "bench $w $lib rc=$rc"; tail -5 gpurun_out/ab_one.err; exit $rc; fi
       python - "$w" "$lib" >> $OUT <<'PY'

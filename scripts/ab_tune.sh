@@ -14,7 +14,7 @@ for rep in 1 2 3; do
       unset FURY_ROW_LIB
       tune="$set"
       case $set in lib:*) export FURY_ROW_LIB=$PWD/fury_amd/libfury_row_${set#lib:}.so; tune="";; esac
-      timeout -k 10 240 python scripts/bench_tuned.py "$tune" --workload $w --steps 30 --warmup 5 \
+      timeout -k 10 240 python scripts/bench_tuned.py "$tune" --full --workload $w --steps 30 --warmup 5 \
         --no-cpu-baseline --no-e2e ${AB_EXTRA:-} > gpurun_out/ab_one.json 2> gpurun_out/ab_one.err
       rc=$?
       if [ $rc -ne 0 ]; then echo "bench $w $set rc=$rc"; tail -5 gpurun_out/ab_one.err; exit $rc; fi

@@ -15,12 +15,12 @@ if [ $rc -gt 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "[gpu_check] smoke rc=$rc" | tee -a $OUT/progress.log; tail -3 $OUT/smoke.log
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
 rc=$?; echo "[gpu_check] bench rc=$rc" | tee -a $OUT/progress.log; tail -3 $OUT/bench.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 if [ "${PROFILE:-1}" = "1" ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv \
-    -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e > $OUT/prof.log 2>&1
+    -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e > $OUT/prof.log 2>&1
   rc=$?; echo "[gpu_check] rocprof rc=$rc" | tee -a $OUT/progress.log; tail -3 $OUT/prof.log
 fi
 echo "[gpu_check] $(date) done" | tee -a $OUT/progress.log

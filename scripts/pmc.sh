@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 240 rocprofv3 --pmc $C -d $OUT/bench_$C -o run --output-format csv \
-    -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > $OUT/bench_$C.log 2>&1 || exit $?
+    -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-e2e > $OUT/bench_$C.log 2>&1 || exit $?
   timeout -k 10 120 rocprofv3 --pmc $C -d $OUT/probe_$C -o run --output-format csv \
     -- tools/hbm_probe 855638016 2 > $OUT/probe_$C.log 2>&1 || exit $?
 done

@@ -14,7 +14,7 @@ for w in ${WORKLOADS:-mixed}; do
   for C in "$P1" "$P2"; do
     i=$((i+1))
     timeout -s KILL 120 rocprofv3 --pmc $C -d $OUT/${w}_$i -o run --output-format csv \
-      -- python3 bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
+      -- python3 bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
       > $OUT/${w}_$i.log 2>&1 || exit $?
     echo "[pmc_var2] $w pass $i done"
   done

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 for w in ${WORKLOADS:-mixed nested}; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 150 rocprofv3 --pmc $C -d $OUT/${w}_$C -o run --output-format csv \
-      -- python3 bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
+      -- python3 bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-e2e \
       > $OUT/${w}_$C.log 2>&1 || exit $?
     echo "[pmc_var_traffic] $w $C done"
   done

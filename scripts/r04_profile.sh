@@ -9,11 +9,11 @@ OUT=gpurun_out/r04p
 mkdir -p $OUT
 export TMPDIR=/tmp
 for w in ${WORKLOADS:-struct100 mixed nested}; do
-  timeout -k 10 240 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e \
+  timeout -k 10 240 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e \
     > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -5 $OUT/bench_$w.err; exit 1; }
   echo "[r04p] bench $w: $(cut -c1-200 $OUT/bench_$w.json)"
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/prof_$w -o $w --output-format csv \
-    -- python3 bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
+    -- python3 bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
     > $OUT/prof_$w.log 2>&1 || { tail -5 $OUT/prof_$w.log; exit 1; }
   echo "[r04p] rocprof $w done"
 done

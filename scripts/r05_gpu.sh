@@ -18,7 +18,7 @@ if [ "${FULL:-1}" = "1" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
 fi
 for w in ${BENCH:-struct100 mixed nested}; do
-  timeout -k 10 300 python bench.py --workload $w --steps 20 --warmup 3 ${BENCH_ARGS:-} > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -5 $OUT/bench_$w.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 20 --warmup 3 ${BENCH_ARGS:-} > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -5 $OUT/bench_$w.err; exit 1; }
   echo "[r05] bench $w: $(cut -c1-200 $OUT/bench_$w.json)"
 done
 echo "[r05] done"

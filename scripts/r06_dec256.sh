@@ -10,8 +10,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for rep in 1 2; do
   for w in mixed nested; do
-    timeout -k 10 200 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/base_${w}_$rep.json 2> $OUT/base_$w.err || { tail -5 $OUT/base_$w.err; exit 1; }
-    FURY_ROW_LIB=$PWD/fury_amd/alt/libfury_row_dec256.so timeout -k 10 200 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/alt_${w}_$rep.json 2> $OUT/alt_$w.err || { tail -5 $OUT/alt_$w.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/base_${w}_$rep.json 2> $OUT/base_$w.err || { tail -5 $OUT/base_$w.err; exit 1; }
+    FURY_ROW_LIB=$PWD/fury_amd/alt/libfury_row_dec256.so timeout -k 10 200 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/alt_${w}_$rep.json 2> $OUT/alt_$w.err || { tail -5 $OUT/alt_$w.err; exit 1; }
     python3 -c "
 import json
 for t in ('base','alt'):

@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for rep in 1 2 3; do
   for v in ${VS:-0 1 2 3 4}; do
-    timeout -k 10 200 python scripts/bench_tuned.py fixed_enc=$v --workload struct100 --steps 30 --warmup 5 --no-cpu-baseline --no-e2e > $OUT/b_${v}_$rep.json 2> $OUT/b_$v.err || { tail -5 $OUT/b_$v.err; exit 1; }
+    timeout -k 10 200 python scripts/bench_tuned.py fixed_enc=$v --full --workload struct100 --steps 30 --warmup 5 --no-cpu-baseline --no-e2e > $OUT/b_${v}_$rep.json 2> $OUT/b_$v.err || { tail -5 $OUT/b_$v.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$OUT/b_${v}_$rep.json').read().strip().splitlines()[-1]); r=d['roofline']

@@ -11,10 +11,10 @@ timeout -k 10 300 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --t
 tail -1 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit $?
 for w in struct100 mixed nested; do
-  timeout -k 10 300 python bench.py --workload $w > $OUT/bench_$w.log 2>&1 || { tail -5 $OUT/bench_$w.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w > $OUT/bench_$w.log 2>&1 || { tail -5 $OUT/bench_$w.log; exit 1; }
   tail -1 $OUT/bench_$w.log
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$w -o $w --output-format csv \
-    -- python3 bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
+    -- python3 bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
     > $OUT/prof_$w.log 2>&1 || exit $?
 done
 echo "[refresh] done"
