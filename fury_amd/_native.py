@@ -67,6 +67,10 @@ SIGNATURES = {
                                                _P]),
     "fury_row_decode": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(FuryColumn), _P]),
     "fury_rows_to_arrow": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(FuryColumn), _P]),
+    "fury_row_project": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64,
+                                        ctypes.POINTER(FuryColumn), _I32, _P]),
+    "fury_row_project_measure": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64,
+                                                ctypes.POINTER(FuryColumn), _P]),
     "fury_schema_num_nodes": (_I32, [_P]),
     "fury_decode_prepare": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(_I64),
                                            ctypes.POINTER(_I64), ctypes.POINTER(_P), _P]),

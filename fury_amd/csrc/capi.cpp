@@ -915,6 +915,163 @@ int fury_rows_to_arrow(const fury_schema* s, const void* rows, const int64_t* ro
   return decode_impl(s, rows, row_offsets, nrows, cols, stream, true, "fury_rows_to_arrow");
 }
 
+// Projected decode (project.hip).  Argument checks + the per-column records of the selection;
+// `measure`: only the offsets of the STRING / BINARY / LIST columns are needed.  The column checks
+// are var_args', with its wording.
+static int project_args(const fury_schema* s, const int32_t* fields, int32_t nsel, const void* rows,
+                        const int64_t* row_offsets, int64_t nrows, const fury_column* cols,
+                        bool need_validity, bool measure, const char* fn, hipStream_t hs,
+                        ProjArgs* a) {
+  const std::string f(fn);
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (nsel <= 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_selected <= 0");
+  if (!fields) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": fields is null");
+  if (nrows > 0 && !cols) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": columns is null");
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a collection schema has no row fields to select (decode it with "
+                         "fury_decode_prepare / fury_decode_execute)");
+  if (nsel > kMaxProjCols)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": at most " + std::to_string(kMaxProjCols) +
+                         " fields per call; for more, run the full decode (fury_row_decode / "
+                         "fury_decode_prepare)");
+  std::vector<char> seen(s->num_fields, 0);
+  for (int j = 0; j < nsel; j++) {
+    const int32_t k = fields[j];
+    if (k < 0 || k >= s->num_fields)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": fields[" + std::to_string(j) + "] = " +
+                                                      std::to_string(k) + " is not a field of the schema");
+    if (seen[k])
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name + ") selected twice");
+    seen[k] = 1;
+  }
+  for (int j = 0; j < nsel; j++) {
+    const int32_t k = fields[j];
+    if (s->plan[k].kind == kOther)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name +
+                           ") is a STRUCT / MAP / LIST of variable-length elements: decode it with "
+                           "fury_decode_prepare / fury_decode_execute");
+  }
+  int st = take_device_error(hs);
+  if (st) return st;
+  *a = ProjArgs{};
+  a->ncols = nsel;
+  a->bitmap_bytes = s->bitmap_bytes;
+  a->fixed_size = s->fixed_size;
+  a->nrows = nrows;
+  a->nt = thread_host_direct() ? 0 : 1;
+  static const fury_column kNoColumn{};
+  for (int j = 0; j < nsel; j++) {
+    const int32_t k = fields[j];
+    const FieldPlan& p = s->plan[k];
+    const fury_column& c = cols ? cols[j] : kNoColumn;
+    ProjCol& v = a->col[j];
+    const std::string who = "column " + std::to_string(j) + " (" + s->fields[k].name + ")";
+    v.kind = p.kind;
+    v.slot = k;
+    v.validity = c.validity;
+    if (c.validity && misaligned(c.validity, 4))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": validity must be 4-byte aligned");
+    if (need_validity && !c.validity)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": Arrow output needs a validity buffer");
+    switch (p.kind) {
+      case kFixed:
+      case kBool:
+        v.width = p.kind == kBool ? 0 : p.width;
+        v.values = static_cast<uint8_t*>(c.values);
+        if (!measure && nrows > 0 && !c.values) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values is null");
+        if (misaligned(c.values, v.width > 1 ? v.width : v.width == 0 ? 4 : 1))
+          return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values misaligned");
+        break;
+      case kBytes:
+        v.width = 1;
+        v.values = static_cast<uint8_t*>(c.values);
+        v.offsets = c.offsets;
+        v.capacity = c.values ? c.capacity : 0;
+        if (nrows > 0 && !c.offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": offsets is null");
+        break;
+      case kDecimal:
+        v.width = 16;
+        v.values = static_cast<uint8_t*>(c.values);
+        if (!measure && nrows > 0 && !c.values) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values is null");
+        if (misaligned(c.values, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values misaligned");
+        break;
+      default: {                    // kListFixed
+        v.width = p.elem_type == FURY_TYPE_BOOL ? 0 : p.elem_width;
+        v.offsets = c.offsets;
+        if (nrows > 0 && !c.offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": offsets is null");
+        if (!c.child) {
+          if (!measure && nrows > 0)
+            return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": list needs a child column");
+        } else {
+          v.values = static_cast<uint8_t*>(c.child->values);
+          v.elem_validity = c.child->validity;
+          // child capacity is in bytes of values; the kernels bound element indices by it
+          v.capacity = !c.child->values ? 0
+                       : v.width == 0   ? c.child->capacity * 8
+                                        : c.child->capacity / v.width;
+          if (misaligned(c.child->validity, 4) || (v.width == 0 && misaligned(c.child->values, 4)))
+            return set_error(FURY_ERR_INVALID_ARGUMENT,
+                             who + ": element bitmaps must be 4-byte aligned");
+          if (need_validity && !measure && !c.child->validity)
+            return set_error(FURY_ERR_INVALID_ARGUMENT,
+                             who + ": Arrow output needs element validity");
+          if (v.width > 1 && misaligned(v.values, v.width))
+            return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": element values misaligned");
+        }
+        break;
+      }
+    }
+  }
+  if (nrows == 0) return FURY_OK;
+  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows is null");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows must be 8-byte aligned");
+  if (!s->is_fixed && !row_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, "variable-length rows need row_offsets");
+  return device_error_word(hs, &a->err);
+}
+
+// An empty batch still yields valid Arrow offsets (offsets[0] = 0), as zero_empty_offsets.
+static int zero_selected_offsets(int32_t nsel, fury_column* cols, hipStream_t hs) {
+  if (!cols) return FURY_OK;
+  for (int j = 0; j < nsel; j++) {
+    if (!cols[j].offsets) continue;
+    const int st = check_hip(hipMemsetAsync(cols[j].offsets, 0, 4, hs), "memset");
+    if (st) return st;
+  }
+  return FURY_OK;
+}
+
+int fury_row_project(const fury_schema* s, const int32_t* fields, int32_t num_selected,
+                     const void* rows, const int64_t* row_offsets, int64_t nrows,
+                     fury_column* cols, int32_t arrow, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  ProjArgs a;
+  const int st = project_args(s, fields, num_selected, rows, row_offsets, nrows, cols, arrow != 0,
+                              false, "fury_row_project", hs, &a);
+  if (st) return st;
+  if (nrows == 0) return zero_selected_offsets(num_selected, cols, hs);
+  // fixed schemas: row i at i * fixed_size, as in fury_row_decode
+  return launch_project(a, static_cast<const uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, hs);
+}
+
+int fury_row_project_measure(const fury_schema* s, const int32_t* fields, int32_t num_selected,
+                             const void* rows, const int64_t* row_offsets, int64_t nrows,
+                             fury_column* cols, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  ProjArgs a;
+  const int st = project_args(s, fields, num_selected, rows, row_offsets, nrows, cols, false, true,
+                              "fury_row_project_measure", hs, &a);
+  if (st) return st;
+  if (nrows == 0) return zero_selected_offsets(num_selected, cols, hs);
+  return launch_project_measure(a, static_cast<const uint8_t*>(rows),
+                                s->is_fixed ? nullptr : row_offsets, hs);
+}
+
 // tuning "wide_engine" (round 6): the engine of a 17-256-field flat variable-length schema's plan --
 // 0 auto (default), 1 the wide tiles (wide.hip), 2 the row walk (walk.hip, field groups past 16
 // counted fields).  Auto takes the walk when the batch's average row (one 8-byte read) exceeds

@@ -451,6 +451,7 @@ int launch_blocks(bool encode, const FixedArgs& a, uint8_t* rows, hipStream_t st
 // 92 / 88 GB/s encode / decode, profiles/r02_host_direct.json).
 static thread_local bool t_host_direct = false;
 void set_thread_host_direct(bool on) { t_host_direct = on; }
+bool thread_host_direct() { return t_host_direct; }
 // tuning "fixed_enc" (round 6 A/B, scripts/r06_fixed_enc.sh, profiles/r06_fixed_enc_ab.txt): the
 // fast-path encode's column gather with 0: 8 loads per lane in flight (rounds 1-5), 2: 16 (the
 // default: Struct-100 encode 0.291 -> 0.286 ms, six alternating runs), 3: 32 (0.291), 4: 16 loads

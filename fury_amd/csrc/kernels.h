@@ -250,6 +250,57 @@ int launch_decode_measure(const VarArgs& a, const uint8_t* rows, const int64_t* 
 // and writes payloads clipped to each column's capacity.
 int launch_decode_var(const VarArgs& a, const uint8_t* rows, const int64_t* row_offsets,
                       hipStream_t stream, bool arrow);
+// ---- projected decode: project.hip -----------------------------------------------------------
+constexpr int kMaxProjCols = 64;      // selected fields per call (the table is in the argument block)
+constexpr int kMaxProjPieces = 40;    // pieces in the argument block; longer lists are uploaded
+
+// One selected field: a VarCol-like record plus the field's slot index in the row.  Indexed
+// wave-uniformly (scalar loads): every member >= 4 bytes, see FixedCol.
+struct ProjCol {
+  uint8_t* values;           // fixed values / BOOL bits / bytes payload / decimal values / list child values
+  uint8_t* validity;         // field validity (Arrow bits) or NULL
+  int32_t* offsets;          // bytes / list offsets (n + 1)
+  uint8_t* elem_validity;    // list element validity or NULL
+  int64_t capacity;          // payload bytes (STRING/BINARY) / child elements (LIST)
+  int32_t kind;              // FieldKind
+  int32_t width;             // fixed: 1/2/4/8; list: element width (0 = bool elements)
+  int32_t slot;              // field index in the schema: bitmap bit, slot at bitmap_bytes + 8 * slot
+  int32_t img;               // LDS image word of the bitmap word | of the slot << 16 (launcher)
+};
+
+// A run of 8-byte words of the row header that the selection reads: at most 16 words (128 B).
+struct ProjPiece {
+  int32_t off;               // byte offset in the row
+  int32_t words;
+};
+
+struct ProjArgs {
+  ProjCol col[kMaxProjCols];
+  ProjPiece piece[kMaxProjPieces];
+  const ProjPiece* ptab;     // device piece list when npieces > kMaxProjPieces, else NULL
+  uint32_t* err;             // the launch stream's device error slot or NULL
+  int64_t nrows;
+  int32_t ncols;
+  int32_t bitmap_bytes;
+  int32_t fixed_size;
+  int32_t nt;                // non-temporal row loads (0 for host-direct calls)
+  // set by the launchers:
+  int32_t npieces;
+  int32_t nwords;            // image words per row (sum of the pieces)
+  int32_t stride;            // image row stride in words (odd)
+  int32_t tile_rows;         // 64 / 128 / 256
+  uint32_t magic;            // 2^32 / nwords + 1: item / nwords by multiply-high
+  int32_t pad_;
+};
+static_assert(sizeof(ProjArgs) <= 4096, "ProjArgs must fit the kernel argument block");
+
+bool thread_host_direct();            // the calling thread's host-direct mode (fixed.hip)
+// row_offsets NULL: row i at i * fixed_size (fixed schemas).  Both are asynchronous on `stream`.
+int launch_project(const ProjArgs& a, const uint8_t* rows, const int64_t* row_offsets,
+                   hipStream_t stream);
+int launch_project_measure(const ProjArgs& a, const uint8_t* rows, const int64_t* row_offsets,
+                           hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

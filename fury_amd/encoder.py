@@ -391,9 +391,12 @@ class RowEncoder:
         """Output columns for fixed-width fields (variable ones are sized by decode_measure).
         Validity and BOOL bitmaps are whole 32-bit words (the kernels store / OR them as words,
         include/fury_row.h: 4-byte aligned, padded to a multiple of 4 bytes)."""
+        return self._alloc_fields(self._schema.fields, nrows, validity)
+
+    def _alloc_fields(self, fields: Sequence[Field], nrows: int, validity: bool) -> List[Column]:
         out = []
         words = ((nrows + 31) // 32) * 4
-        for f in self._schema.fields:
+        for f in fields:
             vb = (torch.empty(words, dtype=torch.uint8, device=self.device)
                   if validity else None)
             if f.type_id == BOOL:
@@ -543,11 +546,12 @@ class RowEncoder:
         return (not self._schema.is_fixed and 16 < nf <= 256
                 and N.lib().fury_get_tuning(b"var_wide") == 1)
 
-    def _size_var_outputs(self, cols: List[Column], n: int, validity: bool, stream) -> None:
+    def _size_var_outputs(self, cols: List[Column], n: int, validity: bool, stream,
+                          fields: Optional[Sequence[Field]] = None) -> None:
         """Allocates the payload / element buffers of the variable-length outputs from the
         offsets fury_row_decode_measure wrote (host read on ``stream``)."""
         with _on(stream):
-            for f, c in zip(self._schema.fields, cols):
+            for f, c in zip(self._schema.fields if fields is None else fields, cols):
                 if f.type_id in (STRING, BINARY):
                     total = int(c.offsets[n].item()) if n else 0
                     c.values = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
@@ -572,13 +576,17 @@ class RowEncoder:
         _check(fn(self._schema.handle, _ptr(batch.rows), _ptr(batch.row_offsets), batch.nrows,
                   _c_columns(cols, keep), sh))
 
-    def check_capacity(self, cols: List[Column], nrows: int) -> None:
+    def check_capacity(self, cols: List[Column], nrows: int,
+                       select: Optional[Sequence] = None) -> None:
         """Raises CapacityError when a decode into preallocated ``cols`` needed more payload
-        (STRING/BINARY bytes, LIST child elements) than the buffers hold (synchronises)."""
+        (STRING/BINARY bytes, LIST child elements) than the buffers hold (synchronises).
+        ``select``: ``cols`` are the outputs of a projected decode of these fields."""
         self.device_status()
-        if self._schema.is_fixed or self.nested or nrows == 0:
+        if nrows == 0 or (select is None and (self._schema.is_fixed or self.nested)):
             return
-        for f, c in zip(self._schema.fields, cols):
+        fields = (self._schema.fields if select is None
+                  else [self._schema.fields[k] for k in self._select(select)])
+        for f, c in zip(fields, cols):
             if f.type_id not in (STRING, BINARY, LIST) or c.offsets is None:
                 continue
             need = int(c.offsets[nrows].item())
@@ -606,6 +614,82 @@ class RowEncoder:
                 f"Schema is not consistent, encoder schema is {self._schema}. self/peer schema "
                 f"hash are {self.schema_hash}/{batch.schema_hash}. Please check writer schema.")
         cols = self._decode(batch, validity, False, stream, out, sizing)
+        self.device_status(stream)
+        return cols
+
+    # -- projected decode: selected fields only (BinaryRow getters over a batch) ---------------
+    def _select(self, select: Sequence) -> List[int]:
+        """Slot indices of ``select`` (field names or slot indices, in selection order)."""
+        names = {f.name: k for k, f in enumerate(self._schema.fields)}
+        out = []
+        for x in select:
+            if isinstance(x, str):
+                if x not in names:
+                    raise IllegalArgumentException(f"no field named {x!r} in {self._schema}")
+                out.append(names[x])
+            else:
+                out.append(int(x))
+        return out
+
+    def alloc_projected(self, select: Sequence, nrows: int, validity: bool = True) -> List[Column]:
+        """Output columns for the selected fields, like ``alloc_columns`` (variable-length ones
+        are sized by ``project_batch``)."""
+        idx = self._select(select)
+        for k in idx:
+            if not 0 <= k < len(self._schema.fields):
+                raise IllegalArgumentException(f"field index {k} is not a field of {self._schema}")
+        return self._alloc_fields([self._schema.fields[k] for k in idx], nrows, validity)
+
+    def project_into(self, batch: RowBatch, select: Sequence, cols: List[Column], stream=None,
+                     arrow: bool = False) -> None:
+        """Decode only the fields ``select`` (names or slot indices, any order) of every row into
+        the preallocated ``cols`` (selection order): one call, no host synchronisation.  Only the
+        bitmap words and slots of the selected fields are read, so the rest of the schema may be
+        anything, nested fields included; payload capacity as in ``decode_into``."""
+        idx = self._select(select)
+        keep: list = []
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        _check(N.lib().fury_row_project(self._schema.handle, sel, len(idx), _ptr(batch.rows),
+                                        _ptr(batch.row_offsets), batch.nrows,
+                                        _c_columns(cols, keep), int(arrow), _stream_handle(stream)))
+
+    def bind_project(self, batch: RowBatch, select: Sequence, cols: List[Column], stream=None,
+                     arrow: bool = False):
+        """``project_into`` bound like ``bind_decode``: descriptors and pointers resolved once."""
+        idx = self._select(select)
+        keep: list = []
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        fn = N.lib().fury_row_project
+        args = (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _c_columns(cols, keep), int(arrow), _stream_handle(stream))
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, sel, batch, cols, self, self._schema)
+        return call
+
+    def project_batch(self, batch: RowBatch, select: Sequence, validity: bool = True, stream=None,
+                      arrow: bool = False) -> List[Column]:
+        """Rows -> the selected columns.  Variable-length outputs are sized exactly
+        (fury_row_project_measure, one host read of the offsets' last entries)."""
+        if batch.schema_hash != self.schema_hash:
+            raise ClassNotCompatibleException(
+                f"Schema is not consistent, encoder schema is {self._schema}. self/peer schema "
+                f"hash are {self.schema_hash}/{batch.schema_hash}. Please check writer schema.")
+        idx = self._select(select)
+        n = batch.nrows
+        validity = validity or arrow
+        with _on(stream):
+            cols = self.alloc_projected(idx, n, validity)
+        fields = [self._schema.fields[k] for k in idx]
+        if any(f.type_id in (STRING, BINARY, LIST) for f in fields):
+            keep: list = []
+            sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+            _check(N.lib().fury_row_project_measure(
+                self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets), n,
+                _c_columns(cols, keep), _stream_handle(stream)))
+            self._size_var_outputs(cols, n, validity, stream, fields)
+        self.project_into(batch, idx, cols, stream, arrow)
         self.device_status(stream)
         return cols
 

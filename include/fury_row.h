@@ -29,6 +29,11 @@
  *                           (FMT/encoder/RowEncoderBuilder.java:185-217,
  *                            FMT/row/binary/UnsafeTrait.java:68-197,
  *                            FMT/row/binary/BinaryArray.java:69-78,157-197)
+ *   fury_row_project        BinaryRow.isNullAt / getInt64 / getString / getDecimal / getArray
+ *   fury_row_project_measure  (ordinal) over a batch, for the selected ordinals only
+ *                           (FMT/row/binary/BinaryRow.java getters,
+ *                            FMT/row/binary/UnsafeTrait.java:68-197,
+ *                            FMT/row/binary/BinaryArray.java:69-78)
  *   fury_rows_to_arrow      ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -200,6 +205,33 @@ int fury_row_decode(const fury_schema* schema, const void* rows, const int64_t* 
  * zero-length entries (ListVector fillHoles, ArrowWriter.java:539,223-225). */
 int fury_rows_to_arrow(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
                        int64_t nrows, fury_column* columns, void* stream);
+
+/* Projected decode -- BinaryRow's getters over a batch (isNullAt / getInt64 / getString /
+ * getDecimal / getArray (ordinal): one bitmap bit and one 8-byte slot per field,
+ * FMT/row/binary/BinaryRow.java getters, FMT/row/binary/UnsafeTrait.java:68-197, an array's header
+ * BinaryArray.pointTo, FMT/row/binary/BinaryArray.java:69-78): decode only the top-level fields
+ * fields[0..num_selected) (slot indices of `schema`, any order, no duplicates) into
+ * columns[0..num_selected), in selection order.  Same column layout, alignment, capacity, error and
+ * `arrow` semantics as fury_row_decode / fury_rows_to_arrow for the same field: a null field leaves
+ * 0 bytes and a cleared validity bit, validity and BOOL bitmaps are written as whole 32-bit words,
+ * payload at or past `capacity` is never written while offsets[nrows] holds the size needed, and a
+ * selected value that lies outside the batch decodes as null and is reported on `stream`
+ * (fury_device_status: FURY_ERR_OUT_OF_BOUNDS).  Only the bitmap words and slots of the selected
+ * fields, and the bytes their values point at, are read: the schema may be flat, wide or nested,
+ * and a corrupt slot of a field that is not selected is not an error.  A selected field must be a
+ * fixed-width scalar, BOOL, STRING / BINARY, DECIMAL or a LIST of fixed-width (or BOOL) elements;
+ * a STRUCT, MAP or LIST of variable-length elements returns FURY_ERR_UNSUPPORTED (decode those
+ * with fury_decode_prepare / fury_decode_execute), as do a collection schema and more than 64
+ * selected fields (run the full decode).  row_offsets may be NULL for is_fixed schemas (row i at
+ * i * fixed_size).  Asynchronous on `stream`, no host synchronisation. */
+int fury_row_project(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
+                     const void* rows, const int64_t* row_offsets, int64_t nrows,
+                     fury_column* columns, int32_t arrow, void* stream);
+/* Pass 1 for sizing: writes only columns[j].offsets of the selected STRING / BINARY / LIST fields
+ * (as fury_row_decode_measure does for all fields). */
+int fury_row_project_measure(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
+                             const void* rows, const int64_t* row_offsets, int64_t nrows,
+                             fury_column* columns, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
