@@ -915,28 +915,20 @@ int fury_rows_to_arrow(const fury_schema* s, const void* rows, const int64_t* ro
   return decode_impl(s, rows, row_offsets, nrows, cols, stream, true, "fury_rows_to_arrow");
 }
 
-// Projected decode (project.hip).  Argument checks + the per-column records of the selection;
-// `measure`: only the offsets of the STRING / BINARY / LIST columns are needed.  The column checks
-// are var_args', with its wording.
-static int project_args(const fury_schema* s, const int32_t* fields, int32_t nsel, const void* rows,
-                        const int64_t* row_offsets, int64_t nrows, const fury_column* cols,
-                        bool need_validity, bool measure, const char* fn, hipStream_t hs,
-                        ProjArgs* a) {
-  const std::string f(fn);
+// The selection checks shared by the projected decode and the in-place update: `coll` / `many`
+// finish the messages for a collection schema and for more than kMaxProjCols fields.
+static int check_selection(const fury_schema* s, const int32_t* fields, int32_t nsel, int64_t nrows,
+                           const void* cols, const std::string& f, const char* coll,
+                           const char* many) {
   if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
   if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
   if (nsel <= 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_selected <= 0");
   if (!fields) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": fields is null");
   if (nrows > 0 && !cols) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": columns is null");
-  if (s->root != 0)
-    return set_error(FURY_ERR_UNSUPPORTED,
-                     f + ": a collection schema has no row fields to select (decode it with "
-                         "fury_decode_prepare / fury_decode_execute)");
+  if (s->root != 0) return set_error(FURY_ERR_UNSUPPORTED, f + ": a collection schema " + coll);
   if (nsel > kMaxProjCols)
     return set_error(FURY_ERR_UNSUPPORTED,
-                     f + ": at most " + std::to_string(kMaxProjCols) +
-                         " fields per call; for more, run the full decode (fury_row_decode / "
-                         "fury_decode_prepare)");
+                     f + ": at most " + std::to_string(kMaxProjCols) + " fields per call; for more, " + many);
   std::vector<char> seen(s->num_fields, 0);
   for (int j = 0; j < nsel; j++) {
     const int32_t k = fields[j];
@@ -948,6 +940,22 @@ static int project_args(const fury_schema* s, const int32_t* fields, int32_t nse
                        f + ": field " + std::to_string(k) + " (" + s->fields[k].name + ") selected twice");
     seen[k] = 1;
   }
+  return FURY_OK;
+}
+
+// Projected decode (project.hip).  Argument checks + the per-column records of the selection;
+// `measure`: only the offsets of the STRING / BINARY / LIST columns are needed.  The column checks
+// are var_args', with its wording.
+static int project_args(const fury_schema* s, const int32_t* fields, int32_t nsel, const void* rows,
+                        const int64_t* row_offsets, int64_t nrows, const fury_column* cols,
+                        bool need_validity, bool measure, const char* fn, hipStream_t hs,
+                        ProjArgs* a) {
+  const std::string f(fn);
+  int st = check_selection(s, fields, nsel, nrows, cols, f,
+                           "has no row fields to select (decode it with fury_decode_prepare / "
+                           "fury_decode_execute)",
+                           "run the full decode (fury_row_decode / fury_decode_prepare)");
+  if (st) return st;
   for (int j = 0; j < nsel; j++) {
     const int32_t k = fields[j];
     if (s->plan[k].kind == kOther)
@@ -956,7 +964,7 @@ static int project_args(const fury_schema* s, const int32_t* fields, int32_t nse
                            ") is a STRUCT / MAP / LIST of variable-length elements: decode it with "
                            "fury_decode_prepare / fury_decode_execute");
   }
-  int st = take_device_error(hs);
+  st = take_device_error(hs);
   if (st) return st;
   *a = ProjArgs{};
   a->ncols = nsel;
@@ -1070,6 +1078,61 @@ int fury_row_project_measure(const fury_schema* s, const int32_t* fields, int32_
   if (nrows == 0) return zero_selected_offsets(num_selected, cols, hs);
   return launch_project_measure(a, static_cast<const uint8_t*>(rows),
                                 s->is_fixed ? nullptr : row_offsets, hs);
+}
+
+// In-place update of selected fixed-width fields (update.hip): BinaryRow's setters over a batch.
+int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_selected, void* rows,
+                    const int64_t* row_offsets, int64_t nrows, const fury_column* cols,
+                    const uint8_t* row_mask, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_update");
+  int st = check_selection(s, fields, num_selected, nrows, cols, f,
+                           "has no row fields to update (re-encode it with fury_row_encode)",
+                           "re-encode the batch (fury_row_encode)");
+  if (st) return st;
+  for (int j = 0; j < num_selected; j++) {
+    const int32_t k = fields[j];
+    if (s->plan[k].kind != kFixed && s->plan[k].kind != kBool)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name +
+                           ") is not fixed-width: variable-length values cannot be updated in "
+                           "place (re-encode the batch with fury_row_encode)");
+  }
+  if (misaligned(row_mask, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask must be 4-byte aligned");
+  st = take_device_error(hs);
+  if (st) return st;
+  ProjArgs a{};
+  a.ncols = num_selected;
+  a.bitmap_bytes = s->bitmap_bytes;
+  a.fixed_size = s->fixed_size;
+  a.nrows = nrows;                    // a.nt stays 0: the update's accesses are plain (update.hip)
+  for (int j = 0; j < num_selected && cols; j++) {
+    const int32_t k = fields[j];
+    const FieldPlan& p = s->plan[k];
+    const fury_column& c = cols[j];
+    ProjCol& v = a.col[j];
+    const std::string who = "column " + std::to_string(j) + " (" + s->fields[k].name + ")";
+    v.kind = p.kind;
+    v.slot = k;
+    v.width = p.kind == kBool ? 0 : p.width;
+    v.values = static_cast<uint8_t*>(c.values);       // inputs: the kernel only reads them
+    v.validity = c.validity;
+    if (c.validity && misaligned(c.validity, 4))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": validity must be 4-byte aligned");
+    if (nrows > 0 && !c.values) return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values is null");
+    if (misaligned(c.values, v.width > 1 ? v.width : v.width == 0 ? 4 : 1))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values misaligned");
+  }
+  if (nrows == 0) return FURY_OK;
+  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows is null");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows must be 8-byte aligned");
+  if (!s->is_fixed && !row_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, "variable-length rows need row_offsets");
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  // fixed schemas: row i at i * fixed_size, as in fury_row_project
+  return launch_update(a, static_cast<uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, row_mask, hs);
 }
 
 // tuning "wide_engine" (round 6): the engine of a 17-256-field flat variable-length schema's plan --

@@ -300,6 +300,19 @@ int launch_project(const ProjArgs& a, const uint8_t* rows, const int64_t* row_of
                    hipStream_t stream);
 int launch_project_measure(const ProjArgs& a, const uint8_t* rows, const int64_t* row_offsets,
                            hipStream_t stream);
+// The launcher-set members of `a` (piece list, image words, stride, tile rows; project.hip); a list
+// longer than kMaxProjPieces is uploaded on `stream` and lives as long as *dt.
+int finish_plan(ProjArgs* a, hipStream_t stream, DeviceTable* dt);
+
+// ---- in-place update of selected fixed-width fields: update.hip ----------------------------------
+// The mirror image of the projected decode, on the same records: ProjCol.values / .validity are the
+// INPUT column of the field (read only; kind kFixed / kBool, width 0 = BOOL bits), the piece list is
+// the list of row words that are rewritten.  row_mask: optional bitmap (bit r = 1: update row r),
+// read as 32-bit words.  Write bounds = "Decode bounds" above applied to stores: a row whose header
+// [base, base + fixed_size) leaves [0, total), or whose own extent (row_offsets[r + 1] - base) is
+// shorter than fixed_size, is not written and raises kErrBounds.  Asynchronous on `stream`.
+int launch_update(const ProjArgs& a, uint8_t* rows, const int64_t* row_offsets,
+                  const uint8_t* row_mask, hipStream_t stream);
 
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block

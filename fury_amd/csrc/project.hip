@@ -373,9 +373,11 @@ __global__ __launch_bounds__(kProjThreads) void project_write(ProjArgs a,
 
 bool is_counted(const ProjCol& c) { return c.kind == kBytes || c.kind == kListFixed; }
 
+}  // namespace
+
 // Piece list, image word of every column's bit and slot, row stride and tile rows of `a`
 // (tile_rows > 0: keep it -- the count pass runs the write pass's tiles).
-void plan(ProjArgs* a, std::vector<ProjPiece>* pieces) {
+static void plan(ProjArgs* a, std::vector<ProjPiece>* pieces) {
   std::vector<int32_t> words;
   for (int k = 0; k < a->ncols; k++) {
     words.push_back(a->col[k].slot >> 6);
@@ -423,6 +425,8 @@ int finish_plan(ProjArgs* a, hipStream_t stream, DeviceTable* dt) {
   }
   return FURY_OK;
 }
+
+namespace {
 
 size_t image_bytes(const ProjArgs& a) { return static_cast<size_t>(a.tile_rows) * a.stride * 8; }
 

@@ -693,6 +693,47 @@ class RowEncoder:
         self.device_status(stream)
         return cols
 
+    # -- in-place update: selected fixed-width fields (BinaryRow setters over a batch) ----------
+    def _update_args(self, batch: RowBatch, select: Sequence, cols: Sequence[Column], row_mask,
+                     stream, keep: list):
+        if batch.schema_hash != self.schema_hash:
+            raise ClassNotCompatibleException(
+                f"Schema is not consistent, encoder schema is {self._schema}. self/peer schema "
+                f"hash are {self.schema_hash}/{batch.schema_hash}. Please check writer schema.")
+        idx = self._select(select)
+        if len(cols) != len(idx):
+            raise IllegalArgumentException(f"{len(idx)} fields selected, {len(cols)} columns given")
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        return (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _c_columns(cols, keep), _ptr(row_mask), _stream_handle(stream))
+
+    def update_fields(self, batch: RowBatch, select: Sequence, cols: Sequence[Column],
+                      row_mask: Optional[torch.Tensor] = None, stream=None) -> None:
+        """Overwrite the fixed-width fields ``select`` (names or slot indices, any order) of every
+        row of ``batch.rows`` in place with the columns ``cols`` (selection order, the layout
+        ``encode_batch`` takes for the same fields): a valid value clears the field's null bit and
+        writes the value's own bytes, a null one sets the bit and zeroes the slot; nothing else of
+        the rows changes.  ``row_mask``: optional device bitmap (LSB-first, whole 32-bit words),
+        bit = 1 updates the row.  One call, no host synchronisation: a row outside the batch is
+        left unwritten and reported by ``device_status(stream)``.  Two updates of one batch must
+        be ordered by the caller (same stream)."""
+        keep: list = []
+        _check(N.lib().fury_row_update(*self._update_args(batch, select, cols, row_mask, stream,
+                                                          keep)))
+
+    def bind_update(self, batch: RowBatch, select: Sequence, cols: Sequence[Column],
+                    row_mask: Optional[torch.Tensor] = None, stream=None):
+        """``update_fields`` bound like ``bind_project``: descriptors and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_update
+        args = self._update_args(batch, select, cols, row_mask, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, cols, row_mask, self, self._schema)
+        return call
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""

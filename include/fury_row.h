@@ -34,6 +34,11 @@
  *                           (FMT/row/binary/BinaryRow.java getters,
  *                            FMT/row/binary/UnsafeTrait.java:68-197,
  *                            FMT/row/binary/BinaryArray.java:69-78)
+ *   fury_row_update         BinaryRow.setBoolean / setByte / setInt16 / setInt32 / setInt64 /
+ *                           setFloat32 / setFloat64 / setDate / setTimestamp / setNullAt /
+ *                           setNotNullAt (ordinal) over a batch, for the selected ordinals only
+ *                           (FMT/row/binary/UnsafeTrait.java:203-266,
+ *                            FMT/row/binary/BinaryRow.java:130-150)
  *   fury_rows_to_arrow      ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -232,6 +237,41 @@ int fury_row_project(const fury_schema* schema, const int32_t* fields, int32_t n
 int fury_row_project_measure(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
                              const void* rows, const int64_t* row_offsets, int64_t nrows,
                              fury_column* columns, void* stream);
+
+/* In-place update -- BinaryRow's setters over a batch (setBoolean / setByte / setInt16 / setInt32 /
+ * setInt64 / setFloat32 / setFloat64 / setDate / setTimestamp, FMT/row/binary/UnsafeTrait.java:203-266;
+ * setNullAt / setNotNullAt, FMT/row/binary/BinaryRow.java:130-150): overwrite the top-level fields
+ * fields[0..num_selected) (slot indices of `schema`, any order, no duplicates) of every row of
+ * `rows` with the input columns columns[0..num_selected), in selection order.  Per row r and
+ * selected field k of width w:
+ *   value valid (validity NULL or bit r = 1)  setX(k, v): bit k of the row's null bitmap is cleared
+ *       and bytes [0, w) of slot k become the little-endian value (BOOL: one byte, 0 or 1; floats as
+ *       raw bits); bytes [w, 8) of the slot stay exactly as they were (0 in any row a writer made);
+ *   value null (bit r = 0)                    setNullAt(k): bit k is set and the 8 slot bytes become 0;
+ *   row_mask given and its bit r = 0          no byte of row r is written.
+ * No other byte changes: other bits of the same bitmap word, other slots, the variable-length
+ * section and padding are never rewritten.  So for rows made by fury_row_encode and no row_mask the
+ * batch equals fury_row_encode of the original columns with the selected ones replaced.
+ * columns[j] follows fury_row_encode's input contract for its field: values = nrows * width bytes,
+ * aligned to the width (BOOL: bit-packed, Arrow), validity optional (NULL = all valid).  The BOOL
+ * values, validity and row_mask bitmaps (LSB-first) are READ as 32-bit words: 4-byte aligned and
+ * readable up to a multiple of 4 bytes.  `rows` is 8-byte aligned; row_offsets may be NULL for
+ * is_fixed schemas (row i at i * fixed_size; a non-NULL row_offsets is ignored for them, as in
+ * fury_row_project).  A selected field must be BOOL, INT8/16/32/64, FLOAT32/64, DATE32 or TIMESTAMP:
+ * STRING / BINARY / DECIMAL / LIST / STRUCT / MAP return FURY_ERR_UNSUPPORTED (a variable-length
+ * value cannot be updated in place: re-encode the batch), as do a collection schema and more than
+ * 64 selected fields.  The rest of the schema may be anything (wide, nested, variable-length).
+ * Bounds: row r is written only when [row_offsets[r], row_offsets[r] + fixed_size) lies inside
+ * [0, row_offsets[nrows]) and row_offsets[r + 1] - row_offsets[r] >= fixed_size; otherwise no byte of
+ * that row is written and FURY_ERR_OUT_OF_BOUNDS is reported on `stream` (fury_device_status).
+ * Nothing outside the batch is ever written.  Rows that overlap through non-monotone offsets get
+ * unspecified contents (never a write outside the batch).  Two updates of the same batch must be
+ * ordered by the caller (same stream, or an event): fields can share a bitmap word, which each call
+ * reads, merges and rewrites.  Asynchronous on `stream`, no host synchronisation; argument errors
+ * are returned before any device work; nrows == 0 returns FURY_OK. */
+int fury_row_update(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
+                    void* rows, const int64_t* row_offsets, int64_t nrows,
+                    const fury_column* columns, const uint8_t* row_mask, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
