@@ -1375,6 +1375,12 @@ int fury_set_tuning(const char* key, int32_t value) {
     set_fixed_enc(value);
     return FURY_OK;
   }
+  if (std::string(key) == "fixed_enc_tail_kib") {
+    if (value < 0 || value > kMaxFixedEncTailKib)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, "fixed_enc_tail_kib: 0..4194304 KiB");
+    set_fixed_enc_tail_kib(value);
+    return FURY_OK;
+  }
   if (std::string(key) == "wide_engine") {
     if (value < 0 || value > 2) return set_error(FURY_ERR_INVALID_ARGUMENT, "wide_engine: 0..2");
     g_wide_engine = value;
@@ -1500,6 +1506,7 @@ int32_t fury_get_tuning(const char* key) {
   if (key && std::string(key) == "wide_enc_engine") return g_wide_enc_engine.load();
   if (key && std::string(key) == "fixed_enc") return fixed_enc();
   if (key && std::string(key) == "fixed_dec") return fixed_dec();
+  if (key && std::string(key) == "fixed_enc_tail_kib") return fixed_enc_tail_kib();
   if (key && std::string(key) == "var_skip") return var_skip();
   if (key && std::string(key) == "var_wide") return var_wide_mode();
   if (key && std::string(key) == "wide_threads") return wide_threads(false);

@@ -19,6 +19,7 @@
 // No MFMA: the kernel is HBM-bound byte movement; LDS only re-shapes the access pattern.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -156,6 +157,23 @@ __device__ __forceinline__ void copy_tile(uint8_t* __restrict__ g, uint8_t* __re
   }
 }
 
+// The encode's row stores of one tile.  The batch's last FixedArgs.tail_tiles tiles (tuning
+// fixed_enc_tail_kib) are stored with the default cache policy, every tile in front of them
+// non-temporally: the measured optimum between all-nt and all-default stores.  The
+// choice is workgroup uniform; kernels without non-temporal stores (general path, host-direct)
+// have one form only.
+template <int NT, int DS>
+__device__ __forceinline__ void store_tile(const FixedArgs& a, uint8_t* __restrict__ g,
+                                           uint8_t* __restrict__ lds, int64_t bytes) {
+  if constexpr ((NT & 2) != 0) {
+    if (gridDim.x - 1 - blockIdx.x < static_cast<unsigned>(a.tail_tiles)) {
+      copy_tile<true, NT & ~2, DS>(g, lds, bytes);
+      return;
+    }
+  }
+  copy_tile<true, NT, DS>(g, lds, bytes);
+}
+
 // kFast: every column is 8 bytes wide and no column carries validity.
 // U = column loads per lane in flight in the gather (8 default, 16 "deep"); P = pair mode
 // (fast path only): a lane moves rows 2q and 2q + 1 of one column with ONE 16-B load, so a
@@ -216,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void encode_fixed_kernel(FixedArgs a,
       }
     }
     __syncthreads();
-    copy_tile<true, NT, DS>(rows + r0 * rs, lds, static_cast<int64_t>(nr) * rs);
+    store_tile<NT, DS>(a, rows + r0 * rs, lds, static_cast<int64_t>(nr) * rs);
     return;
   }
 
@@ -262,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void encode_fixed_kernel(FixedArgs a,
     }
   }
   __syncthreads();
-  copy_tile<true, NT, DS>(rows + r0 * rs, lds, static_cast<int64_t>(nr) * rs);
+  store_tile<NT, DS>(a, rows + r0 * rs, lds, static_cast<int64_t>(nr) * rs);
 }
 
 // D = 16-B row-tile loads per lane in flight (4 default, 16 "deep": the whole 64-row Struct-100
@@ -464,6 +482,15 @@ void set_fixed_dec(int v) { g_fixed_dec = v; }
 int fixed_dec() { return g_fixed_dec; }
 void set_fixed_enc(int v) { g_fixed_enc = v; }
 int fixed_enc() { return g_fixed_enc; }
+// tuning "fixed_enc_tail_kib" (profiles/fixed_tail_ab.jsonl): KiB of trailing row
+// bytes the fast-path encode stores with the default cache policy instead of non-temporally; 0:
+// none (all non-temporal, the earlier behaviour).  Struct-100, 1M rows (816 MB of rows), seven
+// alternating runs, encode ms: 0.288 at 0, 0.277 at 256 MiB, 0.269 at 384, 0.262 at 512 (the
+// default), 0.260 at 640, 0.265 with every row in the window; the decode that follows took
+// 0.252-0.255 ms in every leg.  Host-direct calls ignore it.
+static std::atomic<int> g_fixed_enc_tail_kib{512 * 1024};
+void set_fixed_enc_tail_kib(int v) { g_fixed_enc_tail_kib = v; }
+int fixed_enc_tail_kib() { return g_fixed_enc_tail_kib; }
 
 namespace {
 
@@ -498,21 +525,36 @@ bool pair_ok(const FixedArgs& a) {
   return true;
 }
 
+// Tiles of R rows that lie wholly inside the batch's last fixed_enc_tail_kib KiB of row bytes.
+int32_t tail_tiles_of(const FixedArgs& a, int R) {
+  const int64_t w = static_cast<int64_t>(g_fixed_enc_tail_kib) << 10;
+  if (w == 0 || t_host_direct) return 0;
+  const int64_t tile_bytes = static_cast<int64_t>(R) * a.row_size;
+  const int64_t ntiles = (a.nrows + R - 1) / R;
+  const int64_t head = a.nrows * a.row_size - w;      // bytes in front of the window
+  if (head <= 0) return static_cast<int32_t>(std::min<int64_t>(ntiles, 0x7fffffff));
+  const int64_t first = (head + tile_bytes - 1) / tile_bytes;
+  return static_cast<int32_t>(std::min<int64_t>(std::max<int64_t>(ntiles - first, 0), 0x7fffffff));
+}
+
 }  // namespace
 
 // Kernel choice (round-1/2 A/B sweeps, profiles/r01_ab_fixed*.json, r02_host_direct*.json; the
 // measured-slower pipelined persistent kernels, padded LDS rows, deep encode gather, pair-mode
 // encode and XCD-contiguous tile order were removed in round 3):
-//   fast path (8-byte columns, no validity): non-temporal loads + stores; the encode gathers 16
+//   fast path (8-byte columns, no validity): non-temporal loads + stores, except the row stores
+//     of the encode's tail window (store_tile, tuning fixed_enc_tail_kib); the encode gathers 16
 //     column loads per lane (round 6: 1.7 % faster than 8 on this ROCm; tuning fixed_enc); the decode keeps the whole tile in flight (16 loads per lane) and
 //     stores pairs of rows as 16-B column accesses;
 //   general path (narrow types, validity, > 128 fields): the same tile kernels with per-column
 //     width / validity handling;
 //   host-direct calls: plain loads / stores (see t_host_direct).
-int launch_encode_fixed(const FixedArgs& a, uint8_t* rows, hipStream_t stream, bool fast) {
-  if (a.nrows == 0) return FURY_OK;
-  if (a.ncols > kMaxWideFixedCols) return launch_blocks(true, a, rows, stream);
-  const int R = pick_rows_per_tile(a.row_size);
+int launch_encode_fixed(const FixedArgs& a0, uint8_t* rows, hipStream_t stream, bool fast) {
+  if (a0.nrows == 0) return FURY_OK;
+  if (a0.ncols > kMaxWideFixedCols) return launch_blocks(true, a0, rows, stream);
+  const int R = pick_rows_per_tile(a0.row_size);
+  FixedArgs a = a0;
+  a.tail_tiles = tail_tiles_of(a, R);
 #define FURY_ENC(RR)                                                                          \
   if (R == RR) {                                                                              \
     if (!fast)                                                                                \

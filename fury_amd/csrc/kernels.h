@@ -56,7 +56,8 @@ struct FixedArgs {
   int32_t ncols;
   int32_t bitmap_bytes;
   int32_t row_size;
-  int32_t pad_;
+  int32_t tail_tiles;                 // fast-path encode: trailing tiles stored with the default
+                                      // cache policy; filled by launch_encode_fixed, callers leave 0
   int64_t nrows;
 };
 
@@ -208,6 +209,9 @@ int fixed_enc();                      // tuning "fixed_enc" (fixed.hip)
 void set_fixed_enc(int v);
 int fixed_dec();                      // tuning "fixed_dec" (fixed.hip)
 void set_fixed_dec(int v);
+constexpr int kMaxFixedEncTailKib = 1 << 22;
+int fixed_enc_tail_kib();             // tuning "fixed_enc_tail_kib" (fixed.hip)
+void set_fixed_enc_tail_kib(int v);
 int var_dec_pipe();                   // tuning "var_dec_pipe" (var.hip)
 void set_var_dec_pipe(int v);
 int var_dec_cover();                  // tuning "var_dec_cover" (var.hip): stage coverage, percent

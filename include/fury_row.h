@@ -387,7 +387,9 @@ int fury_trim_workspace(int32_t device);
  * "var_dec_pipe" (0 one tile per workgroup, default; 1 / 2 persistent workgroups with two row
  * stages, the 3- and 6-column instances -- measured slower, kept for A/B).  Fixed-width encode:
  * "fixed_enc" (column loads per lane in flight: 2 = 16, default; 0 = 8; 3 = 32; 4 = 16 with 8
- * stores; 1 = 16-B pair loads).
+ * stores; 1 = 16-B pair loads), "fixed_enc_tail_kib" (KiB of trailing row bytes of a batch that
+ * the fast-path encode stores with the default cache policy, the rows in front of them
+ * non-temporally: 0 .. 4194304, default 524288 = 512 MiB; 0 = every row non-temporal).
  * Host path: "host_decode_inplace" (0 / 1).
  * fury_get_tuning only: "unframe_walks" = streams the walk parsed (wholly or from the first frame
  * the repair could not place), "unframe_repairs" = streams the parallel repair parsed,

@@ -44,7 +44,11 @@ def main():
     root = sys.argv[1]
     res = {"method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes; "
                      "values in KB per dispatch (median over dispatches); calibrated against "
-                     "tools/hbm_probe known-byte kernels", "probe_bytes": PROBE_BYTES}
+                     "tools/hbm_probe known-byte kernels.  Both counters sit on the L2's "
+                     "memory-side requests and appear to include Infinity-Cache hits, so they "
+                     "bound the bytes that leave L2, not the bytes that reach HBM: they cannot "
+                     "show a saving from the Infinity Cache (timing A/Bs are the evidence for "
+                     "those, profiles/fixed_tail_ab.jsonl)", "probe_bytes": PROBE_BYTES}
     pf = per_kernel(load(os.path.join(root, "probe_FETCH_SIZE")), "FETCH_SIZE")
     pw = per_kernel(load(os.path.join(root, "probe_WRITE_SIZE")), "WRITE_SIZE")
     bf = per_kernel(load(os.path.join(root, "bench_FETCH_SIZE")), "FETCH_SIZE")
