@@ -13,6 +13,7 @@
 
 #include "internal.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace fury {
 
@@ -632,8 +633,8 @@ int var_args(const fury_schema* s, const fury_column* cols, int64_t nrows, bool 
     a->tile_rows = encode_tile_rows(*a);
   }
   if (const int e = device_error_word(hs, &a->err)) return e;
-  a->help_now = lookback_help_mode();
-  a->skip = var_skip();
+  a->help_now = knob::lookback_help.load();
+  a->skip = knob::var_skip.load();
   return FURY_OK;
 }
 
@@ -726,22 +727,13 @@ using namespace fury;
 
 extern "C" {
 
-// tuning "wide_enc_engine" (round 6): the encode of a 17-256-field flat variable-length schema -- 0
-// auto, 1 the wide tiles (wide.hip), 2 the row-walk encode (rowenc.hip, as nested schemas).  Auto
-// takes the row walk when the rows' estimated average (the header + each variable-length column's
-// capacity / rows) exceeds "wide_walk_row" bytes, as the decode plan does.  The rows are the same
-// bytes either way (the Java layout).  1M rows, wide vs walk (scripts/ab_wide.py --enc-engines,
-// profiles/r06_wide_enc_engine.jsonl): id + 126 / 70 / 55 / 40 STRING fields (3.2 / 1.8 / 1.4 / 1.0
-// KB rows) 9.56 / 5.22 / 4.10 / 2.59 vs 6.76 / 3.67 / 2.91 / 2.15 ms; the tests' 33-field schema
-// (581 B rows) 0.51 vs 1.07 ms.
-static std::atomic<int> g_wide_enc_engine{0};
-static std::atomic<int> g_wide_walk_row{896};
-
+// The encode of a 17-256-field flat variable-length schema: the wide tiles (wide.hip) or the
+// row-walk encode (rowenc.hip, as nested schemas), by tuning "wide_enc_engine" (tuning.cpp).
 static bool wide_encode_by_walk(const fury_schema* s, const fury_column* cols, int64_t nrows) {
   if (s->generic || s->is_fixed || s->num_fields <= 16 || s->num_fields > kMaxWideVarCols ||
-      !var_wide_mode() || !cols || nrows <= 0)
+      !knob::var_wide.load() || !cols || nrows <= 0)
     return false;
-  const int mode = g_wide_enc_engine.load();
+  const int mode = knob::wide_enc_engine.load();
   if (mode != 0) return mode == 2;
   double row = s->fixed_size;
   for (int k = 0; k < s->num_fields; k++) {
@@ -751,7 +743,7 @@ static bool wide_encode_by_walk(const fury_schema* s, const fury_column* cols, i
     if (kind == kListFixed && cols[k].child && cols[k].child->values)
       row += 16 + static_cast<double>(cols[k].child->capacity) / nrows;
   }
-  return row > g_wide_walk_row.load();
+  return row > knob::wide_walk_row.load();
 }
 
 int fury_row_measure(const fury_schema* s, const fury_column* cols, int64_t nrows,
@@ -1135,16 +1127,6 @@ int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_sel
   return launch_update(a, static_cast<uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, row_mask, hs);
 }
 
-// tuning "wide_engine" (round 6): the engine of a 17-256-field flat variable-length schema's plan --
-// 0 auto (default), 1 the wide tiles (wide.hip), 2 the row walk (walk.hip, field groups past 16
-// counted fields).  Auto takes the walk when the batch's average row (one 8-byte read) exceeds
-// "wide_walk_row" bytes: the wide tiles stage 64 rows in at most 96 KB and read the rest from HBM
-// lane by lane (1M rows, scripts/ab_deep.py --flat / --wide33, profiles/r06_wide_engine.jsonl; id +
-// N STRING fields, wide vs walk: N = 126 / 2.45 KB rows 15.9 vs 6.1 ms, 90 / 1.75 KB 10.0 vs 4.3,
-// 70 / 1.37 KB 5.45 vs 3.34, 55 / 1.07 KB 3.82 vs 2.65, 40 / 785 B 1.72 vs 1.95; the tests'
-// 33-field schema, 520 B: 0.90 vs 1.70).
-static std::atomic<int> g_wide_engine{0};
-
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,
                         int64_t nrows, int64_t* node_entries, int64_t* node_bytes,
                         fury_decode_plan** plan, void* stream) {
@@ -1166,8 +1148,8 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
   // flat variable-length schemas of 17-256 fields: the wide kernels' count pass + scan, kept for
   // the execute (the tile bases), one host sync for the sequence fields' totals
   const bool wide_shape = nrows > 0 && !s->generic && !s->is_fixed && s->num_fields > 16 /* kRegCols: the register-staged kernels below */ &&
-                          s->num_fields <= kMaxWideVarCols && var_wide_mode();
-  int engine = g_wide_engine.load();
+                          s->num_fields <= kMaxWideVarCols && knob::var_wide.load();
+  int engine = knob::wide_engine.load();   // tuning.cpp: 0 auto, 1 the wide tiles, 2 the row walk
   if (wide_shape && engine == 0) {
     int64_t bytes = 0;
     int st = check_hip(hipMemcpyAsync(&bytes, row_offsets + nrows, 8, hipMemcpyDeviceToHost, hs),
@@ -1177,7 +1159,7 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
       delete p;
       return st;
     }
-    engine = bytes > static_cast<int64_t>(g_wide_walk_row.load()) * nrows ? 2 : 1;
+    engine = bytes > static_cast<int64_t>(knob::wide_walk_row.load()) * nrows ? 2 : 1;
   }
   const bool wide = wide_shape && engine != 2;
   if (wide) {
@@ -1304,229 +1286,6 @@ int fury_device_status(void* stream) {
 int fury_stream_release(void* stream) {
   release_error_slot(static_cast<hipStream_t>(stream));
   return FURY_OK;
-}
-
-int fury_set_tuning(const char* key, int32_t value) {
-  if (!key) return set_error(FURY_ERR_INVALID_ARGUMENT, "fury_set_tuning: key is null");
-  if (std::string(key) == "lookback_help") {
-    if (value < 0 || value > 1) return set_error(FURY_ERR_INVALID_ARGUMENT, "lookback_help: 0..1");
-    set_lookback_help_mode(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "unframe") {
-    if (value < 0 || value > 1) return set_error(FURY_ERR_INVALID_ARGUMENT, "unframe: 0..1");
-    set_unframe_mode(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "nested_decode") {
-    if (value < 1 || value > 4)
-      return set_error(FURY_ERR_INVALID_ARGUMENT,
-                       "nested_decode: 1 (level engine), 2 (row walk, level engine beyond it), 3 (row "
-                       "walk, tile BFS beyond it) or 4 (tile BFS)");
-    set_tree_mode(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "bfs_threads") {
-    if (value != 64 && value != 128 && value != 256 && value != 512)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "bfs_threads: 64, 128, 256 or 512");
-    set_bfs_tuning(0, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "bfs_rows") {
-    if (value < 1 || value > 4096) return set_error(FURY_ERR_INVALID_ARGUMENT, "bfs_rows: 1..4096");
-    set_bfs_tuning(1, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "bfs_stage" || std::string(key) == "bfs_arena") {
-    if (value < 0 || value > 128 * 1024)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, std::string(key) + ": 0..131072 bytes (0: auto)");
-    set_bfs_tuning(std::string(key) == "bfs_stage" ? 2 : 3, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "var_dec_cover") {
-    if (value != 0 && (value < 50 || value > 100))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "var_dec_cover: 50..100 (0 = default)");
-    set_var_dec_cover(value ? value : 95);
-    return FURY_OK;
-  }
-  if (std::string(key) == "var_wide") {
-    if (value < 0 || value > 1) return set_error(FURY_ERR_INVALID_ARGUMENT, "var_wide: 0..1");
-    set_var_wide_mode(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "wide_threads" || std::string(key) == "wide_enc_threads") {
-    if (value != 256 && value != 512 && value != 1024)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, std::string(key) + ": 256, 512 or 1024");
-    set_wide_threads(std::string(key) == "wide_enc_threads", value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "var_skip") {
-    if (value < 0 || value > 255) return set_error(FURY_ERR_INVALID_ARGUMENT, "var_skip: 0..255");
-    set_var_skip(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "fixed_dec") {
-    if (value < 0 || value > 3) return set_error(FURY_ERR_INVALID_ARGUMENT, "fixed_dec: 0..3");
-    set_fixed_dec(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "fixed_enc") {
-    if (value < 0 || value > 4) return set_error(FURY_ERR_INVALID_ARGUMENT, "fixed_enc: 0..4");
-    set_fixed_enc(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "fixed_enc_tail_kib") {
-    if (value < 0 || value > kMaxFixedEncTailKib)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "fixed_enc_tail_kib: 0..4194304 KiB");
-    set_fixed_enc_tail_kib(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "wide_engine") {
-    if (value < 0 || value > 2) return set_error(FURY_ERR_INVALID_ARGUMENT, "wide_engine: 0..2");
-    g_wide_engine = value;
-    return FURY_OK;
-  }
-  if (std::string(key) == "wide_enc_engine") {
-    if (value < 0 || value > 2) return set_error(FURY_ERR_INVALID_ARGUMENT, "wide_enc_engine: 0..2");
-    g_wide_enc_engine = value;
-    return FURY_OK;
-  }
-  if (std::string(key) == "wide_walk_row") {
-    if (value < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, "wide_walk_row: bytes >= 0");
-    g_wide_walk_row = value;
-    return FURY_OK;
-  }
-  if (std::string(key) == "var_dec_pipe") {
-    if (value < 0 || value > 2) return set_error(FURY_ERR_INVALID_ARGUMENT, "var_dec_pipe: 0..2");
-    set_var_dec_pipe(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "var_dec_rows") {
-    if (value != 0 && (value < 64 || value > 512 || value % 64))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "var_dec_rows: 0 or 64..512 in steps of 64");
-    set_var_dec_rows(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_threads_write") {
-    if (value != 64 && value != 128 && value != 256 && value != 512)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "walk_threads_write: 64, 128, 256 or 512 (512: no write stage)");
-    set_walk_tuning(6, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_skip") {
-    if (value < 0 || value > 15) return set_error(FURY_ERR_INVALID_ARGUMENT, "walk_skip: 0..15");
-    set_walk_tuning(5, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "host_decode_inplace") {
-    if (value < 0 || value > 1) return set_error(FURY_ERR_INVALID_ARGUMENT, "host_decode_inplace: 0..1");
-    set_host_decode_inplace(value);
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_prefetch") {
-    if (value < 0 || value > 3) return set_error(FURY_ERR_INVALID_ARGUMENT, "walk_prefetch: 0..3 (bit 0 write pass, bit 1 count pass)");
-    set_walk_tuning(4, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_threads") {
-    if (value != 64 && value != 128 && value != 256)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "walk_threads: 64, 128 or 256");
-    set_walk_tuning(0, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_group_k" || std::string(key) == "walk_group_min") {
-    if (value < 0 || value > 256) return set_error(FURY_ERR_INVALID_ARGUMENT, std::string(key) + ": 0..256");
-    set_walk_tuning(std::string(key) == "walk_group_k" ? 8 : 9, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_out") {
-    if (value < 0 || value > 96 * 1024) return set_error(FURY_ERR_INVALID_ARGUMENT, "walk_out: 0..98304 bytes");
-    set_walk_tuning(7, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "walk_stage" || std::string(key) == "walk_pool" ||
-      std::string(key) == "walk_stage_write") {
-    if (value < 0 || value > 96 * 1024)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, std::string(key) + ": 0..98304 bytes");
-    set_walk_tuning(std::string(key) == "walk_stage" ? 1 : std::string(key) == "walk_pool" ? 2 : 3,
-                    static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "tree_debug") {
-    if (value < 0 || value > 1) return set_error(FURY_ERR_INVALID_ARGUMENT, "tree_debug: 0..1");
-    return set_tree_debug(value) ? set_error(FURY_ERR_DEVICE, "tree_debug buffer") : FURY_OK;
-  }
-  if (std::string(key) == "rowenc_rows") {
-    if (value != 128 && value != 256 && value != 512)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "rowenc_rows: 128, 256 or 512");
-    set_rowenc_tuning(0, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "rowenc_tile") {
-    if (value < 0 || value > 256) return set_error(FURY_ERR_INVALID_ARGUMENT, "rowenc_tile: 0..256");
-    set_rowenc_tuning(2, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  if (std::string(key) == "rowenc_img") {
-    if (value < 1024 || value > 152 * 1024)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, "rowenc_img: 1024..155648 bytes");
-    set_rowenc_tuning(1, static_cast<uint32_t>(value));
-    return FURY_OK;
-  }
-  return set_error(FURY_ERR_INVALID_ARGUMENT, std::string("unknown tuning key ") + key);
-}
-
-int32_t fury_get_tuning(const char* key) {
-  if (key && std::string(key) == "lookback_help") return lookback_help_mode();
-  if (key && std::string(key) == "unframe") return unframe_mode();
-  if (key && std::string(key) == "nested_decode") return tree_mode();
-  if (key && std::string(key) == "bfs_threads") return static_cast<int32_t>(bfs_tuning(0));
-  if (key && std::string(key) == "bfs_rows") return static_cast<int32_t>(bfs_tuning(1));
-  if (key && std::string(key) == "bfs_stage") return static_cast<int32_t>(bfs_tuning(2));
-  if (key && std::string(key) == "bfs_arena") return static_cast<int32_t>(bfs_tuning(3));
-  if (key && std::string(key) == "bfs_fallbacks") return static_cast<int32_t>(bfs_tuning(4));
-  if (key && std::string(key) == "rowenc_rows") return static_cast<int32_t>(rowenc_tuning(0));
-  if (key && std::string(key) == "rowenc_img") return static_cast<int32_t>(rowenc_tuning(1));
-  if (key && std::string(key) == "rowenc_tile") return static_cast<int32_t>(rowenc_tuning(2));
-  if (key && std::string(key) == "walk_threads") return static_cast<int32_t>(walk_tuning(0));
-  if (key && std::string(key) == "walk_stage") return static_cast<int32_t>(walk_tuning(1));
-  if (key && std::string(key) == "walk_pool") return static_cast<int32_t>(walk_tuning(2));
-  if (key && std::string(key) == "walk_stage_write") return static_cast<int32_t>(walk_tuning(3));
-  if (key && std::string(key) == "walk_prefetch") return static_cast<int32_t>(walk_tuning(4));
-  if (key && std::string(key) == "walk_threads_write") return static_cast<int32_t>(walk_tuning(6));
-  if (key && std::string(key) == "walk_group_k") return static_cast<int32_t>(walk_tuning(8));
-  if (key && std::string(key) == "walk_group_min") return static_cast<int32_t>(walk_tuning(9));
-  if (key && std::string(key) == "walk_out") return static_cast<int32_t>(walk_tuning(7));
-  if (key && std::string(key) == "walk_skip") return static_cast<int32_t>(walk_tuning(5));
-  if (key && std::string(key) == "host_decode_inplace") return host_decode_inplace();
-  if (key && std::string(key) == "var_dec_rows") return var_dec_rows();
-  if (key && std::string(key) == "var_dec_pipe") return var_dec_pipe();
-  if (key && std::string(key) == "wide_engine") return g_wide_engine.load();
-  if (key && std::string(key) == "wide_walk_row") return g_wide_walk_row.load();
-  if (key && std::string(key) == "wide_enc_engine") return g_wide_enc_engine.load();
-  if (key && std::string(key) == "fixed_enc") return fixed_enc();
-  if (key && std::string(key) == "fixed_dec") return fixed_dec();
-  if (key && std::string(key) == "fixed_enc_tail_kib") return fixed_enc_tail_kib();
-  if (key && std::string(key) == "var_skip") return var_skip();
-  if (key && std::string(key) == "var_wide") return var_wide_mode();
-  if (key && std::string(key) == "wide_threads") return wide_threads(false);
-  if (key && std::string(key) == "wide_enc_threads") return wide_threads(true);
-  if (key && std::string(key) == "var_dec_cover") return var_dec_cover();
-  if (key && std::string(key) == "lookback_timeouts")
-    return static_cast<int32_t>(lookback_timeouts());
-  if (key && std::string(key) == "unframe_walks")
-    return static_cast<int32_t>(unframe_walk_count());
-  if (key && std::string(key) == "host_direct")
-    return static_cast<int32_t>(host_direct_count());
-  if (key && std::string(key) == "err_slots") return error_slots_in_use();
-  if (key && std::string(key) == "err_slots_quarantined") return error_slots_quarantined();
-  if (key && std::string(key) == "thread_key_exits") return thread_key_exits();
-  if (key && std::string(key) == "err_slot_last_key") return last_assigned_key_kind();
-  if (key && std::string(key) == "decode_budget_errors") return static_cast<int32_t>(budget_errors());
-  if (key && std::string(key) == "var_dec_rows_rejected") return var_dec_rows_rejected();
-  if (key && std::string(key) == "unframe_repairs")
-    return static_cast<int32_t>(unframe_repair_count());
-  return -1;
 }
 
 int fury_frame_rows(const fury_schema* s, const void* rows, const int64_t* row_offsets,

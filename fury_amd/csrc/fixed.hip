@@ -24,8 +24,8 @@
 #include <cstring>
 
 #include "internal.h"
-#include <atomic>
 #include "kernels.h"
+#include "tuning.h"
 
 namespace fury {
 
@@ -470,27 +470,6 @@ int launch_blocks(bool encode, const FixedArgs& a, uint8_t* rows, hipStream_t st
 static thread_local bool t_host_direct = false;
 void set_thread_host_direct(bool on) { t_host_direct = on; }
 bool thread_host_direct() { return t_host_direct; }
-// tuning "fixed_enc" (round 6 A/B, scripts/r06_fixed_enc.sh, profiles/r06_fixed_enc_ab.txt): the
-// fast-path encode's column gather with 0: 8 loads per lane in flight (rounds 1-5), 2: 16 (the
-// default: Struct-100 encode 0.291 -> 0.286 ms, six alternating runs), 3: 32 (0.291), 4: 16 loads
-// and 8 16-B stores (0.287); 1: pair mode, 16-B column loads of two rows per lane (0.320)
-static std::atomic<int> g_fixed_enc{2};
-// tuning "fixed_dec" (round 6 A/B): the fast-path decode's column stores per lane in flight, 0: 8
-// (default), 1: 16, 2: 4; 3: 8 with 8 row loads per lane in flight instead of 16
-static std::atomic<int> g_fixed_dec{0};
-void set_fixed_dec(int v) { g_fixed_dec = v; }
-int fixed_dec() { return g_fixed_dec; }
-void set_fixed_enc(int v) { g_fixed_enc = v; }
-int fixed_enc() { return g_fixed_enc; }
-// tuning "fixed_enc_tail_kib" (profiles/fixed_tail_ab.jsonl): KiB of trailing row
-// bytes the fast-path encode stores with the default cache policy instead of non-temporally; 0:
-// none (all non-temporal, the earlier behaviour).  Struct-100, 1M rows (816 MB of rows), seven
-// alternating runs, encode ms: 0.288 at 0, 0.277 at 256 MiB, 0.269 at 384, 0.262 at 512 (the
-// default), 0.260 at 640, 0.265 with every row in the window; the decode that follows took
-// 0.252-0.255 ms in every leg.  Host-direct calls ignore it.
-static std::atomic<int> g_fixed_enc_tail_kib{512 * 1024};
-void set_fixed_enc_tail_kib(int v) { g_fixed_enc_tail_kib = v; }
-int fixed_enc_tail_kib() { return g_fixed_enc_tail_kib; }
 
 namespace {
 
@@ -527,7 +506,7 @@ bool pair_ok(const FixedArgs& a) {
 
 // Tiles of R rows that lie wholly inside the batch's last fixed_enc_tail_kib KiB of row bytes.
 int32_t tail_tiles_of(const FixedArgs& a, int R) {
-  const int64_t w = static_cast<int64_t>(g_fixed_enc_tail_kib) << 10;
+  const int64_t w = static_cast<int64_t>(knob::fixed_enc_tail_kib.load()) << 10;
   if (w == 0 || t_host_direct) return 0;
   const int64_t tile_bytes = static_cast<int64_t>(R) * a.row_size;
   const int64_t ntiles = (a.nrows + R - 1) / R;
@@ -563,16 +542,16 @@ int launch_encode_fixed(const FixedArgs& a0, uint8_t* rows, hipStream_t stream, 
     if (t_host_direct)                                                                        \
       return launch_tile_kernel(encode_fixed_kernel<RR, true, 0>, RR, a.row_size, a.nrows,    \
                                 stream, a, rows);                                             \
-    if (g_fixed_enc == 1 && pair_ok(a))                                                       \
+    if (knob::fixed_enc == 1 && pair_ok(a))                                                   \
       return launch_tile_kernel(encode_fixed_kernel<RR, true, 3, kUnroll, 4, true>, RR,       \
                                 a.row_size, a.nrows, stream, a, rows);                        \
-    if (g_fixed_enc == 2)                                                                     \
+    if (knob::fixed_enc == 2)                                                                 \
       return launch_tile_kernel(encode_fixed_kernel<RR, true, 3, 16>, RR, a.row_size,         \
                                 a.nrows, stream, a, rows);                                    \
-    if (g_fixed_enc == 3)                                                                     \
+    if (knob::fixed_enc == 3)                                                                 \
       return launch_tile_kernel(encode_fixed_kernel<RR, true, 3, 32>, RR, a.row_size,         \
                                 a.nrows, stream, a, rows);                                    \
-    if (g_fixed_enc == 4)                                                                     \
+    if (knob::fixed_enc == 4)                                                                 \
       return launch_tile_kernel(encode_fixed_kernel<RR, true, 3, 16, 8>, RR, a.row_size,      \
                                 a.nrows, stream, a, rows);                                    \
     return launch_tile_kernel(encode_fixed_kernel<RR, true, 3>, RR, a.row_size, a.nrows,      \
@@ -599,13 +578,13 @@ int launch_decode_fixed(const FixedArgs& a, const uint8_t* rows, hipStream_t str
     if (t_host_direct)                                                                        \
       return launch_tile_kernel(decode_fixed_kernel<RR, true, 0>, RR, a.row_size, a.nrows,    \
                                 stream, a, r);                                                \
-    if (pair && g_fixed_dec == 1)                                                             \
+    if (pair && knob::fixed_dec == 1)                                                         \
       return launch_tile_kernel(decode_fixed_kernel<RR, true, 3, 16, true, 16>, RR,           \
                                 a.row_size, a.nrows, stream, a, r);                           \
-    if (pair && g_fixed_dec == 2)                                                             \
+    if (pair && knob::fixed_dec == 2)                                                         \
       return launch_tile_kernel(decode_fixed_kernel<RR, true, 3, 16, true, 4>, RR,            \
                                 a.row_size, a.nrows, stream, a, r);                           \
-    if (pair && g_fixed_dec == 3)                                                             \
+    if (pair && knob::fixed_dec == 3)                                                         \
       return launch_tile_kernel(decode_fixed_kernel<RR, true, 3, 8, true>, RR,                \
                                 a.row_size, a.nrows, stream, a, r);                           \
     return pair ? launch_tile_kernel(decode_fixed_kernel<RR, true, 3, 16, true>, RR,          \

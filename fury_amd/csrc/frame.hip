@@ -29,6 +29,7 @@
 
 #include "internal.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace fury {
 
@@ -568,7 +569,6 @@ __global__ __launch_bounds__(kThreads) void unframe_copy(StreamView sv,
 
 std::atomic<int64_t> g_unframe_walks{0};     // streams parsed (partly) by the sequential walk
 std::atomic<int64_t> g_unframe_repairs{0};   // streams parsed by the parallel repair
-std::atomic<int> g_unframe_mode = 0;   // tuning "unframe": 0 speculative, 1 always walk
 
 struct DevBuf {                               // stream-ordered scratch freed on every exit
   void* p = nullptr;
@@ -692,8 +692,6 @@ int unframe_repair(const uint8_t* in, int64_t len, int64_t n, int64_t hash, int6
 
 }  // namespace
 
-int unframe_mode() { return g_unframe_mode; }
-void set_unframe_mode(int v) { g_unframe_mode = v; }
 int64_t unframe_walk_count() { return g_unframe_walks.load(); }
 int64_t unframe_repair_count() { return g_unframe_repairs.load(); }
 
@@ -716,7 +714,7 @@ int launch_unframe_rows(const uint8_t* in, int64_t len, int64_t n, int64_t hash,
   int st = fpb.alloc(n * 8);
   if (st) return st;
   int64_t* fp = static_cast<int64_t*>(fpb.p);       // frame positions
-  if (len < 12 || g_unframe_mode == 1)
+  if (len < 12 || knob::unframe.load() == 1)   // tuning "unframe" 1: always the walk
     return unframe_walked(in, len, n, hash, 0, fp, rows_out, row_offs, stream);
   const int64_t nb = scan_blocks(len);
   if (nb > 0x7fffffff) return set_error(FURY_ERR_INVALID_ARGUMENT, "stream too large");

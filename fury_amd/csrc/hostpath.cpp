@@ -27,6 +27,7 @@
 
 #include "internal.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace fury {
 namespace {
@@ -824,9 +825,6 @@ bool node_has_offsets(int32_t t) {
 }  // namespace
 
 int64_t host_direct_count() { return g_host_direct.load(); }
-static std::atomic<int> g_host_decode_inplace{0};
-void set_host_decode_inplace(int v) { g_host_decode_inplace.store(v); }
-int host_decode_inplace() { return g_host_decode_inplace.load(); }
 
 // The stream-ordered pool of `device` keeps freed workspace memory instead of returning it at
 // every synchronisation (the default release threshold 0 re-mapped ~1.7 GB per call).  Once per
@@ -938,7 +936,7 @@ int fury_decode_host_execute(fury_decode_plan* p, fury_column* host) {
   // decode's scattered 4-8 byte stores over PCIe ran at 27.5 GB/s end to end against 40.4 GB/s for
   // HBM outputs + copies (1M nested rows, scripts/ab_host_nested.py).
   std::vector<uint8_t> copy_off(nn, 1), copy_val(nn, 1);
-  const bool inplace = host_decode_inplace();
+  const bool inplace = knob::host_decode_inplace.load();
   bool all_direct = inplace;
   for (int i = 0; i < nn; i++) {
     const GenTpl& t = s->nodes[i];

@@ -200,27 +200,7 @@ int workspace_reserve(size_t bytes, void** out);
 // Rows per encode tile for this column set (the staged per-row inputs must fit the LDS pool).
 int encode_tile_rows(const VarArgs& a);
 int64_t lookback_timeouts();
-void set_host_decode_inplace(int v);   // tuning "host_decode_inplace" (hostpath.cpp)
-int host_decode_inplace();
-int var_dec_rows();                   // tuning "var_dec_rows" (var.hip): 0 = planned
-void set_var_dec_rows(int v);
-int var_dec_rows_rejected();          // forced tiles whose images did not fit (plan used instead)
-int fixed_enc();                      // tuning "fixed_enc" (fixed.hip)
-void set_fixed_enc(int v);
-int fixed_dec();                      // tuning "fixed_dec" (fixed.hip)
-void set_fixed_dec(int v);
-constexpr int kMaxFixedEncTailKib = 1 << 22;
-int fixed_enc_tail_kib();             // tuning "fixed_enc_tail_kib" (fixed.hip)
-void set_fixed_enc_tail_kib(int v);
-int var_dec_pipe();                   // tuning "var_dec_pipe" (var.hip)
-void set_var_dec_pipe(int v);
-int var_dec_cover();                  // tuning "var_dec_cover" (var.hip): stage coverage, percent
-void set_var_dec_cover(int v);
-int lookback_help_mode();
-int var_wide_mode();                  // tuning "var_wide" (var.hip): 1 count + write passes, 0 look-back tiles
-void set_var_wide_mode(int v);
-int wide_threads(bool encode);        // tuning "wide_threads" / "wide_enc_threads" (var.hip)
-void set_wide_threads(bool encode, int v);
+int var_dec_rows_rejected();          // forced "var_dec_rows" tiles whose images did not fit (plan used)
 // offsets_only: fury_row_decode_measure (the Arrow offsets of the variable-length fields only)
 // Plan form of the wide decode (fury_decode_prepare / _execute): the count pass + scan once, the
 // per-tile bases kept for the write pass.
@@ -239,9 +219,6 @@ int launch_decode_wide(const VarArgs& a, const uint8_t* rows, const int64_t* off
                        bool offsets_only);
 int launch_encode_wide(const VarArgs& a, const int64_t* offs, uint8_t* rows, int64_t cap,
                        hipStream_t stream);
-int var_skip();                       // tuning "var_skip" (diagnostics, timing only)
-void set_var_skip(int v);
-void set_lookback_help_mode(int v);
 int launch_measure_rows(const VarArgs& a, int64_t* row_offsets, hipStream_t stream);
 // Rows at the offsets fury_row_measure produced; never writes row bytes at or past `cap`.
 int launch_encode_var(const VarArgs& a, const int64_t* row_offsets, uint8_t* rows, int64_t cap,
@@ -353,8 +330,6 @@ constexpr int kRowEncMaxDepth = 5;
 constexpr int kMaxNestLevels = 64;     // schema nesting limit (schema.cpp)
 int rowenc_launch(const GenArgs& g, const int64_t* offs, int64_t* sizes, uint8_t* rows,
                   int64_t cap, hipStream_t stream);
-void set_rowenc_tuning(int which, uint32_t v);   // 0 "rowenc_rows", 1 "rowenc_img", 2 "rowenc_tile"
-uint32_t rowenc_tuning(int which);
 // Level-by-level nested decode (levels.hip): prepare = per-level count / scan / expand passes
 // (totals[2 i] entries, totals[2 i + 1] payload bytes of node i), execute = one write pass into
 // the outputs of gen_args' node table.
@@ -372,16 +347,8 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
 int tree_execute(const TreePlan* p, const GenNode* outs, const uint8_t* rows, const int64_t* offs,
                  const std::vector<int64_t>& totals, hipStream_t hs);
 void tree_free(TreePlan* p);
-void set_tree_mode(int v);           // tuning "nested_decode": 1 levels, 2 row walk (default), 3 walk + BFS, 4 BFS
-void set_bfs_tuning(int which, uint32_t v);   // bfs_threads / bfs_rows / bfs_stage / bfs_arena
-int64_t bfs_tuning(int which);                // ... and 4: bfs_fallbacks
-int tree_mode();
+int64_t bfs_fallbacks();             // tile-BFS batches whose tiles overflowed the arena
 int set_tree_debug(int on);          // tuning "tree_debug": phase accumulators on / off
-// tunings of the row-walk decode (walk.hip): 0 "walk_threads" (128 / 256 rows per tile),
-// 1 "walk_stage" (LDS stage cap of the count pass, bytes), 2 "walk_pool" (LDS bitmap-window
-// bytes), 3 "walk_stage_write" (LDS stage cap of the write pass), 4 "walk_prefetch" (bit 0 write pass, bit 1 count pass)
-void set_walk_tuning(int which, uint32_t v);
-uint32_t walk_tuning(int which);
 uint64_t* tree_debug_buffer();
 // Exclusive scan of s[0..n) with the total stored to *total (device); ws: scan_workspace(n).
 int64_t scan_workspace(int64_t n);
@@ -390,11 +357,7 @@ void device_scan(int64_t* s, int64_t n, int64_t* total, int64_t* ws, hipStream_t
 int launch_frame_rows(const uint8_t* rows, const int64_t* row_offsets, int64_t nrows,
                       int64_t fixed_size, int64_t schema_hash, uint8_t* out,
                       int64_t* frame_offsets, hipStream_t stream);
-// Unframe mode (tuning "unframe"): 0 speculative parallel parse (sequential walk on failure),
-// 1 always the sequential walk; unframe_walk_count() = streams the walk has parsed.
-int unframe_mode();
-void set_unframe_mode(int v);
-int64_t unframe_walk_count();
+int64_t unframe_walk_count();        // streams the sequential walk has parsed (tuning "unframe")
 void keep_pool(int device);      // hostpath.cpp: keep freed stream-pool memory pooled
 int64_t host_direct_count();     // hostpath.cpp: host calls run directly on pinned memory
 int64_t unframe_repair_count();      // streams parsed by the parallel repair (pointer doubling)

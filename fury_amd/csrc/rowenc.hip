@@ -26,22 +26,17 @@
 // row bytes (partial lines); only the rows past the image (rowenc_img) are built in HBM.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <vector>
 
 #include "internal.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace fury {
 
 namespace {
 
 constexpr int kRwThreads = 256;                 // measure pass rows per workgroup
-std::atomic<int> g_rw_rows = 256;                            // tuning "rowenc_rows": build-pass rows per workgroup
-                                                             // (512 with a 152 KB image: 1.31 vs 1.33 ms, not the default)
-std::atomic<uint32_t> g_rw_img = 76 * 1024;                  // tuning "rowenc_img": its LDS image bytes
-std::atomic<int> g_rw_tile = 0;                              // tuning "rowenc_tile": rows per workgroup (0: all)
 
 template <class T>
 using Lds = __attribute__((address_space(3))) T;
@@ -527,10 +522,10 @@ int rowenc_launch(const GenArgs& g, const int64_t* offs, int64_t* sizes, uint8_t
   a.nrows = g.nrows;
   a.cap = cap;
   a.ntop = g.ntop;
-  a.img = g_rw_img;
-  int nt = sizes ? kRwThreads : g_rw_rows.load();
+  a.img = knob::rowenc_img.load();
+  int nt = sizes ? kRwThreads : knob::rowenc_rows.load();
   if (nlev > kRowEncMaxDepth && nt > 256) nt = 256;   // the explicit-stack instances: 128 / 256
-  const int rt = g_rw_tile.load();
+  const int rt = knob::rowenc_tile.load();
   a.tile = sizes ? nt : (rt > 0 && rt < nt ? rt : nt);
   const dim3 grid(static_cast<unsigned>((g.nrows + a.tile - 1) / a.tile));
   auto go = [&](auto meas, auto enc128, auto enc256, auto enc512) {
@@ -583,16 +578,6 @@ int launch_gen_encode(const GenArgs& g, const int64_t* offs, uint8_t* rows, int6
                       hipStream_t stream) {
   if (g.nrows == 0) return FURY_OK;
   return rowenc_launch(g, offs, nullptr, rows, cap, stream);
-}
-
-void set_rowenc_tuning(int which, uint32_t v) {
-  if (which == 0) g_rw_rows = static_cast<int>(v);
-  else if (which == 1) g_rw_img = (v + 15) & ~15u;
-  else g_rw_tile = static_cast<int>(v);
-}
-uint32_t rowenc_tuning(int which) {
-  return which == 0 ? static_cast<uint32_t>(g_rw_rows) : which == 1 ? g_rw_img.load()
-         : static_cast<uint32_t>(g_rw_tile);
 }
 
 }  // namespace fury

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "tree_dev.h"
+#include "tuning.h"
 
 namespace fury {
 
@@ -102,64 +103,12 @@ int tree_host_width(int32_t t) {
   }
 }
 
-// tuning "nested_decode": 1 level engine; 2 row walk, the level engine past its limits (default);
-// 3 row walk, tile BFS (bfs.hip) past its limits; 4 tile BFS always (A/B, tests).  The BFS falls
-// back to the walk / level engine for a batch whose tiles overflow its arena.  Measured round 6
-// (profiles/r06_*): at depth 3 the walk decodes 4M rows in 2.53 ms, the BFS in 3.06 ms
-// at best (its per-level chains of LDS round trips run at ~2 waves per SIMD, bounded by the LDS
-// its staged tiles take); past the walk's limits the level engine beat the BFS too (depth 6-20,
-// 128 counted nodes), so the BFS is not the default anywhere.
-std::atomic<int> g_tree_mode = 2;
-// Tile BFS defaults (tunings "bfs_threads", "bfs_rows", "bfs_stage" (0: sized from the batch's
-// average row), "bfs_arena" (0: 60 % of the stage + 2 KB)).
-std::atomic<int> g_bfs_threads = 128;
-std::atomic<int> g_bfs_rows = 128;
-std::atomic<uint32_t> g_bfs_stage{0};
-std::atomic<uint32_t> g_bfs_arena{0};
 std::atomic<int64_t> g_bfs_fallbacks{0};      // batches whose tiles overflowed the arena
-// Row-walk defaults from scripts/ab_generic.py legs at 4M depth-3 rows: 128-row count tiles with
-// a 12 KB stage (prepare 1.35 -> 1.08 ms: more tiles resident), 256-row write tiles (1.87 -> 1.78
-// ms) with the prefetch; round 5: 512-row unstaged write tiles with 24 KB output windows (1.67 ->
-// 1.62 ms: the tile prologue -- bases, window layout -- is ~16 % of a 256-row tile's time), then
-// 40 KB windows (the same time, WRITE 1.34x -> 1.23x the column bytes).
-std::atomic<int> g_walk_threads = 128;        // tuning "walk_threads": rows (= threads) per count tile
-std::atomic<int> g_walk_threads_w = 512;      // tuning "walk_threads_write": rows per write tile (a multiple)
-std::atomic<uint32_t> g_walk_stage = 12 * 1024;  // tuning "walk_stage": LDS stage cap of a row-walk count tile
-std::atomic<uint32_t> g_walk_stage_w = 0;        // tuning "walk_stage_write": the same for the write pass (its
-                                    // LDS-bound occupancy costs more than HBM row reads save)
-std::atomic<uint32_t> g_walk_pool = 8 * 1024;    // tuning "walk_pool": LDS bitmap-window bytes (write pass)
-std::atomic<uint32_t> g_walk_out{40 * 1024};     // tuning "walk_out": LDS output-window bytes (write pass)
-std::atomic<int> g_walk_prefetch = 1;            // tuning "walk_prefetch": waves pull their rows into L2 first
-                                    // (bit 0: write pass, bit 1: count pass)
-std::atomic<int> g_walk_skip = 0;                // tuning "walk_skip": diagnostics (TreeArgs.skip)
-// Field groups (round 6): a schema with more than "walk_group_min" counted slots walks its
-// top-level fields in groups of about "walk_group_k" slots, a workgroup per (tile, group): the LDS
-// cursors (4 B x slots x rows) of a 128-slot bean held one 64-row count tile per ~5 waves of a CU.
-// 1M beans of 128 / 200 counted nodes (scripts/r06_group2.sh): one group 22.5 / 39.0 ms, groups
-// of 16 / 8 / 4 / 2 slots 9.7 / 7.2 / 6.8 / 6.9 and 13.8 / 10.2 / 10.2 / 10.2 ms, the level engine
-// 16.5 / 25.7 ms.  The depth-3 schema (9 slots) in groups of 4 / 2 / 1: 2.64 / 2.99 / 3.25 vs
-// 2.53 ms -- at <= 16 slots the cursors do not limit the tiles per CU, so it stays one group.
-// With the payload windows (late round 6, profiles/r06_walk_group_size_payload_windows.jsonl)
-// groups of 8 took over: 128 counted nodes 6.52 vs 6.89 ms (4), flat id + 126 STRING fields 5.83
-// vs 6.14; 200 counted nodes 9.47 (4 doubles to 8 there: at most 32 groups).
-std::atomic<int> g_walk_group_k = 8;     // tuning "walk_group_k" (0 = one group)
-std::atomic<int> g_walk_group_min = 16;  // tuning "walk_group_min"
 uint64_t* g_tree_dbg = nullptr;  // tuning "tree_debug": phase accumulators (device, 80 words)
 
 }  // namespace
 
-void set_tree_mode(int v) { g_tree_mode = v; }
-void set_bfs_tuning(int which, uint32_t v) {
-  if (which == 0) g_bfs_threads = static_cast<int>(v);
-  else if (which == 1) g_bfs_rows = static_cast<int>(v);
-  else if (which == 2) g_bfs_stage = (v + 15) & ~15u;
-  else g_bfs_arena = (v + 15) & ~15u;
-}
-int64_t bfs_tuning(int which) {
-  return which == 0 ? g_bfs_threads.load() : which == 1 ? g_bfs_rows.load()
-         : which == 2 ? static_cast<int64_t>(g_bfs_stage.load())
-         : which == 3 ? static_cast<int64_t>(g_bfs_arena.load()) : g_bfs_fallbacks.load();
-}
+int64_t bfs_fallbacks() { return g_bfs_fallbacks.load(); }
 uint64_t* tree_debug_buffer() { return g_tree_dbg; }
 int set_tree_debug(int on) {
   if (on && !g_tree_dbg) {
@@ -170,28 +119,6 @@ int set_tree_debug(int on) {
     g_tree_dbg = nullptr;
   }
   return FURY_OK;
-}
-int tree_mode() { return g_tree_mode; }
-void set_walk_tuning(int which, uint32_t v) {
-  if (which == 0) g_walk_threads = static_cast<int>(v);
-  else if (which == 1) g_walk_stage = (v + 15) & ~15u;
-  else if (which == 2) g_walk_pool = (v + 15) & ~15u;
-  else if (which == 3) g_walk_stage_w = (v + 15) & ~15u;
-  else if (which == 4) g_walk_prefetch = static_cast<int>(v);
-  else if (which == 5) g_walk_skip = static_cast<int>(v);
-  else if (which == 7) g_walk_out = (v + 15) & ~15u;
-  else if (which == 8) g_walk_group_k = static_cast<int>(v);
-  else if (which == 9) g_walk_group_min = static_cast<int>(v);
-  else g_walk_threads_w = static_cast<int>(v);
-}
-uint32_t walk_tuning(int which) {
-  return which == 0 ? static_cast<uint32_t>(g_walk_threads) : which == 1 ? g_walk_stage.load()
-         : which == 2 ? g_walk_pool.load() : which == 3 ? g_walk_stage_w.load()
-         : which == 4 ? static_cast<uint32_t>(g_walk_prefetch)
-         : which == 5 ? static_cast<uint32_t>(g_walk_skip)
-         : which == 7 ? g_walk_out.load()
-         : which == 8 ? static_cast<uint32_t>(g_walk_group_k)
-         : which == 9 ? static_cast<uint32_t>(g_walk_group_min) : static_cast<uint32_t>(g_walk_threads_w);
 }
 
 struct TreePlan {
@@ -249,7 +176,7 @@ int tree_launch(const TreePlan& p, bool write, const TNode* dev_nodes, const uin
   a.dbg = tree_debug_buffer();
   a.stride = p.stride;
   a.prefetch = (p.prefetch >> (write ? 0 : 1)) & 1;
-  a.skip = write ? g_walk_skip.load() : 0;
+  a.skip = write ? knob::walk_skip.load() : 0;
   a.rowpre = p.rowpre;
   a.K = p.K;
   a.pool_cap = p.pool_cap;
@@ -288,7 +215,7 @@ int bfs_prepare(TreePlan* p, const uint8_t* rows, const int64_t* offs, int64_t n
   if (!st) st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize");
   if (st) return st;
   const int64_t bytes = std::max<int64_t>(pin[2 * kTreeMaxNodes + 1], 0);
-  const int nt = g_bfs_threads.load();
+  const int nt = knob::bfs_threads.load();
   const double avg = static_cast<double>(bytes) / static_cast<double>(nrows);
   DeviceTable dt;
   st = upload_table(p->nodes.data(), p->nodes.size() * sizeof(TNode), hs, &dt);
@@ -297,13 +224,13 @@ int bfs_prepare(TreePlan* p, const uint8_t* rows, const int64_t* offs, int64_t n
   // (container-heavy rows need ~16 B of records per container entry); after three tries the batch
   // goes to the row walk / level engine.
   for (int attempt = 0; attempt < 3; attempt++) {
-    const int trows = std::max(1, g_bfs_rows.load() >> attempt);
+    const int trows = std::max(1, knob::bfs_rows.load() >> attempt);
     if (attempt > 0 && trows < 16) break;
-    uint32_t stage = g_bfs_stage.load();
+    uint32_t stage = static_cast<uint32_t>(knob::bfs_stage.load());
     if (!stage)
       stage = static_cast<uint32_t>(std::min<double>(std::max<double>(avg * trows * 1.05 + 64, 2048), 64 * 1024));
     stage = (stage + 15) & ~15u;
-    uint32_t arena = g_bfs_arena.load();
+    uint32_t arena = static_cast<uint32_t>(knob::bfs_arena.load());
     if (!arena)
       arena = ((static_cast<uint32_t>((attempt == 0 ? 0.6 : 1.5) * stage) + 2048) + 15) & ~15u;
     while (bfs_lds(nn, nt, stage, arena, trows) > kWalkLdsMax && arena > 1024) arena /= 2;
@@ -358,7 +285,7 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
                  hipStream_t hs, TreePlan** out, std::vector<int64_t>* totals) {
   *out = nullptr;
   const int nn = static_cast<int>(s->nodes.size());
-  if (g_tree_mode == 1 || nn > kTreeMaxNodes || nrows <= 0)
+  if (knob::nested_decode == 1 || nn > kTreeMaxNodes || nrows <= 0)
     return FURY_OK;
   // counted slots (row walk): LIST / MAP elements, STRING / BINARY payload bytes
   int K = 0;
@@ -367,7 +294,8 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
     if (t == FURY_TYPE_LIST || t == FURY_TYPE_MAP || t == FURY_TYPE_STRING || t == FURY_TYPE_BINARY) K++;
   }
   const bool walk_ok = K <= kWalkMaxK && s->depth <= kWalkMaxDepth;
-  const bool bfs_ok = !s->root && (g_tree_mode == 4 || (g_tree_mode == 3 && !walk_ok));
+  const bool bfs_ok =
+      !s->root && (knob::nested_decode == 4 || (knob::nested_decode == 3 && !walk_ok));
   if (!walk_ok && !bfs_ok) return FURY_OK;                          // the level engine
   TreePlan* p = new TreePlan();
   p->K = K;
@@ -411,10 +339,10 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
     std::vector<int32_t> kn(kf.size() + 1, 0);  // first slot of each subtree
     for (size_t f = 0; f < kf.size(); f++) kn[f + 1] = kn[f] + kf[f];
     // field groups: consecutive top-level fields, about walk_group_k slots each, at most kMaxGroups
-    const int gk0 = g_walk_group_k.load();
+    const int gk0 = knob::walk_group_k.load();
     p->ngrp = 1;
     p->gf[0] = p->gk[0] = 0;
-    if (gk0 > 0 && K > g_walk_group_min.load() && ntop > 1 && !s->root) {
+    if (gk0 > 0 && K > knob::walk_group_min.load() && ntop > 1 && !s->root) {
       for (int target = gk0;; target *= 2) {
         int g = 0, acc = 0;
         for (int f = 0; f < ntop && g < kMaxGroups; f++) {
@@ -490,25 +418,26 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
   }
   // a thread per row; the stage holds the tile's rows up to walk_stage bytes (the rest are read
   // from HBM), the bitmap-window pool walk_pool bytes
-  p->nt = g_walk_threads;
+  p->nt = knob::walk_threads.load();
   // Field groups read only their fields' slots and payloads: the L2 pull of whole rows (per group)
   // and the count stage cost more than they save (1M beans of 128 counted nodes, groups of 4:
   // 9.9 -> 7.1 ms without the pull, 6.9 ms without the stage too; scripts/r06_group2.sh)
-  p->prefetch = p->ngrp > 1 ? 0 : g_walk_prefetch.load();
-  const uint32_t cstage = p->ngrp > 1 ? 0u : (g_walk_stage + 15) & ~15u;
+  p->prefetch = p->ngrp > 1 ? 0 : knob::walk_prefetch.load();
+  // (the LDS byte knobs hold multiples of 16: fury_set_tuning rounds them up)
+  const uint32_t cstage = p->ngrp > 1 ? 0u : static_cast<uint32_t>(knob::walk_stage.load());
   // the count pass's per-row counters (4 B x counted nodes x rows) must fit one workgroup too:
   // a bean of ~200+ STRING fields counts on 64-row tiles
   while (p->nt > 64 &&
          walk_count_lds(nn, p->Kl, p->nt, cstage, (p->prefetch & 2) != 0) > kWalkLdsMax)
     p->nt /= 2;
-  const int tw = g_walk_threads_w.load();
+  const int tw = knob::walk_threads_write.load();
   p->ntw = tw % p->nt == 0 && tw >= p->nt ? tw : p->nt;
   p->tile_rows = p->nt;
   p->stage_cap = cstage;
-  p->stage_cap_w = (g_walk_stage_w + 15) & ~15u;
+  p->stage_cap_w = static_cast<uint32_t>(knob::walk_stage_write.load());
   if (p->ntw > 256 && p->stage_cap_w) p->ntw = 256;   // 512-row write tiles: unstaged instance only
-  p->pool_cap = g_walk_pool;
-  p->out_cap = g_walk_out;
+  p->pool_cap = static_cast<uint32_t>(knob::walk_pool.load());
+  p->out_cap = static_cast<uint32_t>(knob::walk_out.load());
   // The write pass's LDS (cursors: K x rows, node tables, windows) must fit one workgroup: wide
   // schemas (many counted nodes / nodes) step down the tile rows, then the windows.
   const bool pfw = (p->prefetch & 1) != 0;

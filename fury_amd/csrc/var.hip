@@ -5,6 +5,7 @@
 #define FURY_VAR_MAIN
 #include <atomic>
 #include "var_dev.h"
+#include "tuning.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -63,11 +64,6 @@ int launch_measure_rows(const VarArgs& a, int64_t* offs, hipStream_t stream) {
 // observed: workgroups are dispatched in launch order).  Synchronous device read.
 int64_t lookback_timeouts() { return device_error_count(); }
 
-// Test hook (tuning "lookback_help"): every look-back computes a silent predecessor's aggregate
-// at once -- the path a late-dispatched predecessor takes -- instead of polling first.
-static std::atomic<int> g_help_now = 0;
-int lookback_help_mode() { return g_help_now; }
-void set_lookback_help_mode(int v) { g_help_now = v; }
 // Rows per register-staged tile: the estimated tile bytes (row sizes from the input buffers' byte
 // counts, as plan_encode_pipe) fit the LDS image with headroom.
 int reg_tile_rows(const VarArgs& a) {
@@ -128,7 +124,7 @@ int launch_encode_var(const VarArgs& a, const int64_t* offs, uint8_t* rows, int6
     const int64_t nt = (a.nrows + b.tile_rows - 1) / b.tile_rows;
     return launch_encode_var_reg(b, const_cast<int64_t*>(offs), rows, cap, nt, reg_mode(a), nullptr,
                                  stream);
-  } else if (var_wide_mode()) {   // 64-row tiles, fields round robin over the waves (wide.hip)
+  } else if (knob::var_wide.load()) {   // 64-row tiles, fields round robin over the waves (wide.hip)
     return launch_encode_wide(a, offs, rows, cap, stream);
   } else if (a.tab) {          // wider than the argument block: column table in device memory
     hipLaunchKernelGGL(encode_var_kernel<MetaMapWide>, dim3(nb), dim3(kEncRows), 0, stream, a,
@@ -165,7 +161,7 @@ int launch_decode_measure(const VarArgs& a, const uint8_t* rows, const int64_t* 
   for (int k = 0; k < a.ncols; k++)
     if (hcol(a, k).kind == kBytes || hcol(a, k).kind == kListFixed) nseq++;
   if (nseq == 0 || a.nrows == 0) return FURY_OK;
-  if (a.ncols > kRegCols && var_wide_mode()) return launch_decode_wide(a, rows, offs, stream, true);
+  if (a.ncols > kRegCols && knob::var_wide.load()) return launch_decode_wide(a, rows, offs, stream, true);
   const int64_t nb = nblocks(a.nrows);
   int64_t* ws = nullptr;
   const int64_t scr = scan_workspace(nb);
@@ -181,36 +177,8 @@ int launch_decode_measure(const VarArgs& a, const uint8_t* rows, const int64_t* 
   return st;
 }
 
-static std::atomic<int> g_dec_rows = 0;
-// tuning "var_skip" (diagnostics: phases of encode_var_reg (1 / 2 / 4) and decode_var_reg (16 / 32 /
-// 64 / 128) skipped, outputs WRONG; timing only)
-static std::atomic<int> g_var_skip{0};
-static std::atomic<int> g_var_wide{1};
-// threads per 64-row tile of the wide kernels (ab_wide legs, 33 fields x 5M rows): decode 256
-// (3.22 vs 3.37 ms at 512), encode 512 (2.20 vs 2.78 ms at 256)
-static std::atomic<int> g_wide_threads[2] = {256, 512};
-int wide_threads(bool encode) { return g_wide_threads[encode ? 1 : 0].load(); }
-void set_wide_threads(bool encode, int v) { g_wide_threads[encode ? 1 : 0] = v; }
-int var_wide_mode() { return g_var_wide.load(); }
-void set_var_wide_mode(int v) { g_var_wide = v; }
-int var_skip() { return g_var_skip.load(); }
-void set_var_skip(int v) { g_var_skip = v; }
 static std::atomic<int> g_dec_rows_rejected{0};
 int var_dec_rows_rejected() { return g_dec_rows_rejected.load(); }
-int var_dec_rows() { return g_dec_rows; }
-void set_var_dec_rows(int v) { g_dec_rows = v; }
-// tuning "var_dec_cover": percent of a tile's estimated row bytes the stage must hold (the rest
-// is read from HBM by the rows' threads).  95 (scripts/ab_dec.py legs, interleaved): mixed 10M
-// 0.542 -> 0.508 ms (its tiles grow 448 -> 512 rows), C4 4M unchanged (0.229 ms); 80 or less slows C4.
-static std::atomic<int> g_dec_cover = 95;
-// tuning "var_dec_pipe" (round 6): 0 one tile per workgroup; 1 persistent
-// workgroups with two row stages of the planned size (fewer workgroups per CU); 2 the same with
-// the planned LDS split into images + two half stages (the tile rows shrink to fit)
-static std::atomic<int> g_dec_pipe = 0;
-int var_dec_pipe() { return g_dec_pipe; }
-void set_var_dec_pipe(int v) { g_dec_pipe = v; }
-int var_dec_cover() { return g_dec_cover; }
-void set_var_dec_cover(int v) { g_dec_cover = v; }
 
 // Tile plan of decode_var_reg: rows per tile (a multiple of 64, <= kDecThreads), LDS bytes of the
 // output images and of the row stage, within the LDS of two workgroups per CU.  Per-row sizes are
@@ -243,8 +211,8 @@ void dec_tile_plan(const VarArgs& a, int* tile, uint32_t* img, uint32_t* stage, 
   // headroom over the estimates: 8 % on the images, 2 % on the stage (a 512-row tile's bytes
   // vary by ~1 %; C4 0.252 -> 0.229 ms against 15 % / 5 %, mixed unchanged)
   const double mi = 1.08, mr = 1.02;
-  if (g_dec_rows > 0) {                         // tuning "var_dec_rows": forced tile rows (A/B)
-    const int R = g_dec_rows;
+  if (knob::var_dec_rows.load() > 0) {          // tuning "var_dec_rows": forced tile rows (A/B)
+    const int R = knob::var_dec_rows.load();
     const int64_t im = (static_cast<int64_t>(img_row * R * mi + img_fix) + 1023) & ~int64_t(1023);
     // a forced tile whose estimated images exceed half the budget is not run with clipped images
     // (that would change which overflow path an A/B leg measures): the plan below is used and the
@@ -260,7 +228,7 @@ void dec_tile_plan(const VarArgs& a, int* tile, uint32_t* img, uint32_t* stage, 
   for (int R = kDecThreads; R >= 64; R -= 64) {
     const int64_t im = (static_cast<int64_t>(img_row * R * mi + img_fix) + 1023) & ~int64_t(1023);
     const int64_t st = ((kBudget - im) / (pipe == 2 ? 2 : 1)) & ~int64_t(15);
-    if (st >= static_cast<int64_t>(row * R * mr * g_dec_cover / 100.0) + 64 || R == 64) {
+    if (st >= static_cast<int64_t>(row * R * mr * knob::var_dec_cover.load() / 100.0) + 64 || R == 64) {
       *tile = R;
       *img = static_cast<uint32_t>(std::min<int64_t>(im, kBudget / 2));
       *stage = static_cast<uint32_t>(((kBudget - *img) / (pipe == 2 ? 2 : 1)) & ~int64_t(15));
@@ -281,7 +249,7 @@ int launch_decode_var(const VarArgs& a, const uint8_t* rows, const int64_t* offs
   if (a.ncols <= kRegCols) {
     VarArgs b = a;
     uint32_t img = 0, stage = 0;
-    b.dec_pipe = dec_pipe_k(reg_dec_k(a.ncols)) ? g_dec_pipe.load() : 0;
+    b.dec_pipe = dec_pipe_k(reg_dec_k(a.ncols)) ? knob::var_dec_pipe.load() : 0;
     dec_tile_plan(a, &b.tile_rows, &img, &stage, b.dec_pipe);
     const int64_t nt = (a.nrows + b.tile_rows - 1) / b.tile_rows;
     // status words: tiles x K (the instance's column count), zeroed per launch
@@ -296,7 +264,7 @@ int launch_decode_var(const VarArgs& a, const uint8_t* rows, const int64_t* offs
   }
   // wider than kRegCols: count pass + scan + write pass (wide.hip); tuning "var_wide" 0 = the
   // round-4 256-row look-back tile kernel below (A/B)
-  if (var_wide_mode()) return launch_decode_wide(a, rows, offs, stream, false);
+  if (knob::var_wide.load()) return launch_decode_wide(a, rows, offs, stream, false);
   // look-back status words (nb x nseq), zeroed per launch
   const size_t wsb = (nb * nseq + 1) * 8;
   uint64_t* ws = nullptr;

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "var_dev.h"
+#include "tuning.h"
 
 namespace fury {
 
@@ -635,7 +636,7 @@ int launch_encode_wide(const VarArgs& a, const int64_t* offs, uint8_t* rows, int
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nt)), dim3(threads), lds, stream, a, offs,
                        rows, cap, img);
   };
-  const int th = wide_threads(true);
+  const int th = knob::wide_enc_threads.load();
   if (th == 1024) go(wide_encode_kernel<1024>, 1024);
   else if (th == 512) go(wide_encode_kernel<512>, 512);
   else go(wide_encode_kernel<256>, 256);
@@ -785,7 +786,7 @@ WideGeom wide_geom(const VarArgs& a, double avg_row) {
     if (c.kind == kListFixed) row += 12 + per * (c.width == 0 ? 1 : c.width) + 4;
   }
   const uint32_t bit_cap = ((kWideImg / 8 + 4 * 16) + 15) & ~15u;
-  const int th = wide_threads(false);
+  const int th = knob::wide_threads.load();
   const uint32_t imgs = static_cast<uint32_t>(th / 64) * (kWideImg + bit_cap);
   // the stage: the tile's estimated row bytes (+3 %), at least 1 KB, at most 96 KB (rows past it
   // are read from HBM)

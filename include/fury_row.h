@@ -357,47 +357,59 @@ int fury_trim_workspace(int32_t device);
 
 /* ---- tuning (no reference equivalent) ---------------------------------------------------- */
 /* Process-wide knobs for tests and A/B measurement (results are identical under every value,
- * except the diagnostic "walk_skip").
- * Key "lookback_help": 1 = every look-back of the variable-length decode computes a silent
+ * except the diagnostics "walk_skip" and "var_skip").  fury_set_tuning returns FURY_OK, or
+ * FURY_ERR_INVALID_ARGUMENT for an unknown key or a value outside the key's legal values (the
+ * knob keeps its value; fury_last_error names the legal ones).  Byte sizes marked (16) are stored,
+ * and read back, rounded up to a multiple of 16.  fury_get_tuning returns the value, or -1 for an
+ * unknown key.
+ * Key "lookback_help" (0 / 1): 1 = every look-back of the variable-length decode computes a silent
  * predecessor tile's aggregate at once (the path a late-dispatched predecessor takes).
  * Key "unframe": 0 speculative parallel stream parse (a stream that does not verify -- a payload
  * spelling a plausible header -- is repaired in parallel; the sequential walk only reports
  * errors), 1 always the sequential walk.
  * Nested engines: "nested_decode" 2 row walk (default), 1 level engine (schemas past the walk's
  * limits -- 5 levels, 256 counted nodes -- use it by themselves), 3 row walk with the tile BFS past
- * its limits, 4 tile BFS ("bfs_threads" 64 / 128 / 256 / 512, "bfs_rows", "bfs_stage", "bfs_arena"
- * bytes, 0 = sized from the batch; fury_get_tuning "bfs_fallbacks" = batches whose tiles outgrew
- * the arena and went to the walk / level engine); nested encode is the row walk with an explicit-stack continuation
- * for deep schemas: "rowenc_rows" (128 / 256 / 512 threads per group), "rowenc_tile" (rows per group,
- * 0 = threads), "rowenc_img" (LDS image bytes); row-walk decode "walk_threads" /
- * "walk_threads_write" (128 / 256 / 512), "walk_stage" / "walk_stage_write" / "walk_pool" / "walk_out"
- * (LDS bytes), "walk_prefetch" (bit 0 write pass, bit 1 count pass), "walk_group_k" /
- * "walk_group_min" (a schema with more than walk_group_min counted nodes, default 16, walks its
- * top-level fields in groups of about walk_group_k counted nodes, default 8, a workgroup per tile
- * and group; 0 = one group); flat schemas of 17-256
- * fields: "var_wide" (1 wide tiles, default; 0 generic var tiles), "wide_engine" (the plan's engine
- * for them: 0 auto -- the row walk when the batch's average row exceeds "wide_walk_row" bytes,
- * default 896 --, 1 wide tiles, 2 row walk; "wide_enc_engine" the same for the encode, by the
- * columns' estimated row), "wide_threads" /
- * "wide_enc_threads" (256 / 512 / 1024); diagnostics "var_skip" (register-staged encode / decode phases
- * skipped: outputs WRONG, timing only),
- * "tree_debug" (phase clocks) and "walk_skip" (bitmask of write-pass phases skipped: outputs
- * WRONG, timing only).  Variable-length decode tile plan: "var_dec_cover" (percent of a tile's
- * row bytes the LDS stage must hold, default 95), "var_dec_rows" (forced tile rows, 0 = plan),
+ * its limits, 4 tile BFS ("bfs_threads" 64 / 128 / 256 / 512, default 128; "bfs_rows" 1 .. 4096,
+ * default 128; "bfs_stage", "bfs_arena" 0 .. 131072 bytes (16), 0 = sized from the batch;
+ * fury_get_tuning "bfs_fallbacks" = batches whose tiles outgrew the arena and went to the walk /
+ * level engine); nested encode is the row walk with an explicit-stack continuation for deep
+ * schemas: "rowenc_rows" (128 / 256 / 512 threads per group, default 256), "rowenc_tile" (rows per
+ * group, 0 .. 256, 0 = threads), "rowenc_img" (LDS image bytes, 1024 .. 155648 (16), default
+ * 77824); row-walk decode "walk_threads" (64 / 128 / 256, default 128), "walk_threads_write" (64 /
+ * 128 / 256 / 512, default 512), "walk_stage" / "walk_stage_write" / "walk_pool" / "walk_out" (LDS
+ * bytes, 0 .. 98304 (16); defaults 12288 / 0 / 8192 / 40960), "walk_prefetch" (0 .. 3: bit 0 write
+ * pass, default; bit 1 count pass), "walk_group_k" / "walk_group_min" (0 .. 256: a schema with more
+ * than walk_group_min counted nodes, default 16, walks its top-level fields in groups of about
+ * walk_group_k counted nodes, default 8, a workgroup per tile and group; 0 = one group); flat
+ * schemas of 17-256 fields: "var_wide" (1 wide tiles, default; 0 generic var tiles), "wide_engine"
+ * (the plan's engine for them: 0 auto -- the row walk when the batch's average row exceeds
+ * "wide_walk_row" bytes, any value >= 0, default 896 --, 1 wide tiles, 2 row walk;
+ * "wide_enc_engine" the same for the encode, by the columns' estimated row), "wide_threads" /
+ * "wide_enc_threads" (256 / 512 / 1024, defaults 256 / 512); diagnostics "var_skip" (0 .. 255,
+ * register-staged encode / decode phases skipped: outputs WRONG, timing only), "tree_debug" (0 / 1,
+ * phase clocks; set only, fury_get_tuning returns -1) and "walk_skip" (0 .. 15, bitmask of
+ * write-pass phases skipped: outputs WRONG, timing only).  Variable-length decode tile plan:
+ * "var_dec_cover" (percent of a tile's row bytes the LDS stage must hold, 50 .. 100, default 95; 0
+ * sets the default), "var_dec_rows" (forced tile rows, 64 .. 512 in steps of 64, 0 = plan),
  * "var_dec_pipe" (0 one tile per workgroup, default; 1 / 2 persistent workgroups with two row
  * stages, the 3- and 6-column instances -- measured slower, kept for A/B).  Fixed-width encode:
  * "fixed_enc" (column loads per lane in flight: 2 = 16, default; 0 = 8; 3 = 32; 4 = 16 with 8
  * stores; 1 = 16-B pair loads), "fixed_enc_tail_kib" (KiB of trailing row bytes of a batch that
  * the fast-path encode stores with the default cache policy, the rows in front of them
  * non-temporally: 0 .. 4194304, default 524288 = 512 MiB; 0 = every row non-temporal).
+ * Fixed-width decode: "fixed_dec" (0 = 8 column stores per lane in flight, default; 1 = 16; 2 = 4;
+ * 3 = 8 with 8 row loads per lane in flight instead of 16).
  * Host path: "host_decode_inplace" (0 / 1).
- * fury_get_tuning only: "unframe_walks" = streams the walk parsed (wholly or from the first frame
- * the repair could not place), "unframe_repairs" = streams the parallel repair parsed,
+ * fury_get_tuning only (fury_set_tuning refuses them as unknown keys): "unframe_walks" = streams
+ * the walk parsed (wholly or from the first frame the repair could not place), "unframe_repairs" =
+ * streams the parallel repair parsed,
  * "host_direct" = fury_row_encode_host / _decode_host calls that ran their kernels directly on
  * pinned host buffers (fixed-width and flat variable-length schemas, no staging),
  * "lookback_timeouts" = decoupled look-backs that gave up (must stay 0; synchronous device read),
  * "err_slots" = device error slots held by live streams (fury_stream_release),
  * "err_slots_quarantined" = slots of exited threads waiting for a device synchronisation,
+ * "thread_key_exits" = threads that exited holding per-thread slot keys, "err_slot_last_key" = the
+ * key the last slot was assigned under (0 a stream handle, 1 a thread's key) -- diagnostics,
  * "decode_budget_errors" = nested decodes refused by the item budget (a device limit),
  * "var_dec_rows_rejected" = forced "var_dec_rows" tiles whose images did not fit (planned tile used). */
 int fury_set_tuning(const char* key, int32_t value);
