@@ -1127,6 +1127,84 @@ int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_sel
   return launch_update(a, static_cast<uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, row_mask, hs);
 }
 
+// Row selection (take.hip): BinaryRow.copy() over a batch.  The host checks both calls share; `n` =
+// output rows the copy may have to produce (take: num_selected, filter: nrows).
+static int take_args(const fury_schema* s, const void* rows, const int64_t* row_offsets,
+                     int64_t nrows, int64_t n, void* out_rows, int64_t out_capacity,
+                     int64_t* out_offsets, const std::string& f, TakeArgs* a) {
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (!s->is_fixed && !row_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
+  if (!s->is_fixed && !out_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need out_offsets");
+  if (n > 0 && nrows > 0 && out_rows && !rows)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  if (s->is_fixed && out_rows && s->fixed_size > 0 && out_capacity / s->fixed_size < n)
+    return set_error(FURY_ERR_CAPACITY,
+                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(n) +
+                         " rows of " + std::to_string(s->fixed_size) + " bytes");
+  *a = TakeArgs{};
+  a->rows = static_cast<const uint8_t*>(rows);
+  a->row_offsets = s->is_fixed ? nullptr : row_offsets;   // fixed schemas: row i at i * fixed_size
+  a->nrows = nrows;
+  a->fixed_size = s->fixed_size;
+  a->out = static_cast<uint8_t*>(out_rows);
+  a->cap = out_rows ? out_capacity : 0;
+  a->out_offsets = out_offsets;
+  return FURY_OK;
+}
+
+int fury_row_take(const fury_schema* s, const void* rows, const int64_t* row_offsets, int64_t nrows,
+                  const int64_t* indices, int64_t num_selected, void* out_rows,
+                  int64_t out_capacity, int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_take");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (num_selected < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_selected < 0");
+  if (num_selected > 0 && !indices) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": indices is null");
+  if (misaligned(indices, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": indices must be 8-byte aligned");
+  TakeArgs a;
+  int st = take_args(s, rows, row_offsets, nrows, num_selected, out_rows, out_capacity, out_offsets,
+                     f, &a);
+  if (st) return st;
+  st = take_device_error(hs);
+  if (st) return st;
+  a.indices = indices;
+  a.n = num_selected;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_take(a, hs);
+}
+
+int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_offsets,
+                    int64_t nrows, const uint8_t* row_mask, void* out_rows, int64_t out_capacity,
+                    int64_t* out_offsets, int64_t* out_count, int64_t* out_indices, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_filter");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (nrows > 0 && !row_mask) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask is null");
+  if (misaligned(row_mask, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask must be 4-byte aligned");
+  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
+  if (misaligned(out_count, 8) || misaligned(out_indices, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count / out_indices must be 8-byte aligned");
+  TakeArgs a;
+  int st = take_args(s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, f, &a);
+  if (st) return st;
+  st = take_device_error(hs);
+  if (st) return st;
+  a.n = nrows;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_filter(a, row_mask, out_count, out_indices, hs);
+}
+
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,
                         int64_t nrows, int64_t* node_entries, int64_t* node_bytes,
                         fury_decode_plan** plan, void* stream) {

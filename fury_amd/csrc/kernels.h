@@ -295,6 +295,33 @@ int finish_plan(ProjArgs* a, hipStream_t stream, DeviceTable* dt);
 int launch_update(const ProjArgs& a, uint8_t* rows, const int64_t* row_offsets,
                   const uint8_t* row_mask, hipStream_t stream);
 
+// ---- row selection: take.hip -------------------------------------------------------------------
+// Gathers whole rows (BinaryRow.copy() over a batch): output row j = the bytes of source row
+// indices[j].  row_offsets NULL: fixed-size rows (row i at i * fixed_size, output row j at
+// j * fixed_size; out_offsets optional).  out NULL: the measure form, only out_offsets is written.
+// Bounds = "Decode bounds" above: a source row is read only when its index is in [0, nrows) and its
+// extent lies in [0, row_offsets[nrows]) with a size >= 0 that is a multiple of 8; otherwise the
+// output row has size 0 (fixed-size rows: zero bytes) and kErrBounds is raised.  Output bytes at or
+// past `cap` are never written while out_offsets is always complete.  Asynchronous on `stream`.
+struct TakeArgs {
+  const uint8_t* rows;
+  const int64_t* row_offsets;         // NULL for fixed-size rows
+  int64_t nrows;
+  int64_t fixed_size;
+  const int64_t* indices;             // take: n of them (device)
+  int64_t n;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // take: n + 1 entries; filter: nrows + 1
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+int launch_take(const TakeArgs& a, hipStream_t stream);
+// Keeps the rows whose mask bit (LSB-first, read as 32-bit words) is 1, in row order: *out_count
+// rows; out_offsets entries past the count repeat the total, out_indices (optional, nrows entries)
+// holds the kept row numbers and -1 past the count.  The count is never read by the host.
+int launch_filter(const TakeArgs& a, const uint8_t* row_mask, int64_t* out_count,
+                  int64_t* out_indices, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

@@ -734,6 +734,131 @@ class RowEncoder:
         call.keep = (keep, batch, cols, row_mask, self, self._schema)
         return call
 
+    # -- row selection: whole rows gathered into a new batch (BinaryRow.copy() over a batch) -----
+    def _check_hash(self, batch: RowBatch) -> None:
+        if batch.schema_hash != self.schema_hash:
+            raise ClassNotCompatibleException(
+                f"Schema is not consistent, encoder schema is {self._schema}. self/peer schema "
+                f"hash are {self.schema_hash}/{batch.schema_hash}. Please check writer schema.")
+
+    def _indices(self, indices, stream) -> torch.Tensor:
+        if not isinstance(indices, torch.Tensor):
+            indices = torch.as_tensor(np.asarray(indices, dtype=np.int64))
+        if indices.dtype in (torch.bool, torch.float16, torch.float32, torch.float64,
+                             torch.bfloat16):
+            raise IllegalArgumentException(f"indices must be an integer tensor, not {indices.dtype}")
+        with _on(stream):
+            return indices.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+
+    def _take_args(self, batch: RowBatch, indices, out_rows, out_offsets, stream, keep: list):
+        self._check_hash(batch)
+        idx = self._indices(indices, stream)
+        keep.append(idx)
+        return (self._schema.handle, _ptr(batch.rows), _ptr(batch.row_offsets), batch.nrows,
+                _ptr(idx), idx.numel(), _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets),
+                _stream_handle(stream))
+
+    def take_into(self, batch: RowBatch, indices, out_rows: Optional[torch.Tensor],
+                  out_offsets: Optional[torch.Tensor] = None, stream=None) -> None:
+        """Output row j = the bytes of row ``indices[j]`` of ``batch`` (any integer tensor, any
+        order, repeats allowed), written to the preallocated ``out_rows`` (capacity = its size)
+        with their offsets in ``out_offsets`` (int64, ``len(indices) + 1`` entries; optional for
+        fixed-width schemas): one call, no host synchronisation.  Bytes at or past the capacity
+        are not written while ``out_offsets`` is always complete; ``out_rows=None`` only measures.
+        An index outside the batch gives a 0-byte row, reported by ``device_status(stream)``.
+        ``out_rows`` must not overlap ``batch.rows``."""
+        keep: list = []
+        _check(N.lib().fury_row_take(*self._take_args(batch, indices, out_rows, out_offsets, stream,
+                                                      keep)))
+
+    def bind_take(self, batch: RowBatch, indices, out_rows: Optional[torch.Tensor],
+                  out_offsets: Optional[torch.Tensor] = None, stream=None):
+        """``take_into`` bound like ``bind_update``: pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_take
+        args = self._take_args(batch, indices, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def take(self, batch: RowBatch, indices, stream=None) -> RowBatch:
+        """The rows ``indices`` of ``batch`` as a new batch.  Fixed-width schemas know the size up
+        front; the others measure first (one host read of the byte total), then copy."""
+        self._check_hash(batch)
+        idx = self._indices(indices, stream)
+        n = idx.numel()
+        with _on(stream):
+            if self._schema.is_fixed:
+                offs = None
+                total = n * self._schema.fixed_size
+            else:
+                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                self.take_into(batch, idx, None, offs, stream)
+                total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.take_into(batch, idx, rows, offs, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, self.schema_hash)
+
+    def _mask_words(self, row_mask: torch.Tensor, nrows: int, stream) -> torch.Tensor:
+        """``row_mask`` as the device bitmap the kernels read (LSB-first, whole 32-bit words): a
+        uint8 bitmap is taken as it is, a bool tensor of ``nrows`` entries is packed."""
+        if row_mask is None or row_mask.dtype != torch.bool:
+            return row_mask
+        if row_mask.numel() != nrows:
+            raise IllegalArgumentException(f"row_mask has {row_mask.numel()} entries for {nrows} rows")
+        with _on(stream):
+            m = torch.zeros(((nrows + 31) // 32) * 32, dtype=torch.uint8, device=self.device)
+            m[:nrows] = row_mask.to(self.device).reshape(-1)
+            w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=self.device)
+            return (m.reshape(-1, 8) * w).sum(dim=1, dtype=torch.int32).to(torch.uint8)
+
+    def filter_into(self, batch: RowBatch, row_mask: torch.Tensor,
+                    out_rows: Optional[torch.Tensor], out_offsets: Optional[torch.Tensor],
+                    out_count: torch.Tensor, out_indices: Optional[torch.Tensor] = None,
+                    stream=None) -> None:
+        """Keeps the rows of ``batch`` whose ``row_mask`` bit is 1 (device bitmap, LSB-first, whole
+        32-bit words; or a bool tensor), in row order: one call, no host synchronisation.
+        ``out_count`` (int64[1]) receives the number kept, ``out_offsets`` (int64, nrows + 1
+        entries; optional for fixed-width schemas) the offsets -- entries past the count repeat the
+        total -- and ``out_indices`` (optional, int64, nrows entries) the row numbers kept, -1
+        past the count.  Capacity and ``out_rows=None`` as in ``take_into``."""
+        self._check_hash(batch)
+        mask = self._mask_words(row_mask, batch.nrows, stream)
+        _check(N.lib().fury_row_filter(
+            self._schema.handle, _ptr(batch.rows), _ptr(batch.row_offsets), batch.nrows, _ptr(mask),
+            _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets), _ptr(out_count),
+            _ptr(out_indices), _stream_handle(stream)))
+
+    def filter(self, batch: RowBatch, row_mask: torch.Tensor, stream=None,
+               return_indices: bool = False):
+        """The rows of ``batch`` whose ``row_mask`` bit is 1 as a new batch (with
+        ``return_indices``: and their row numbers).  The mask is compacted and measured on the
+        device, count and byte total come back in one host read, then the kept rows are copied."""
+        self._check_hash(batch)
+        n = batch.nrows
+        fixed = self._schema.is_fixed
+        with _on(stream):
+            head = torch.empty(2, dtype=torch.int64, device=self.device)      # count, total
+            idx = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            offs = None if fixed else torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            self.filter_into(batch, row_mask, None, offs, head[:1], idx[:n] if n else None, stream)
+            if fixed:
+                count = int(head[0].item())
+                total = count * self._schema.fixed_size
+            else:
+                head[1:] = offs[n:]
+                count, total = (int(x) for x in head.cpu())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            kept = idx[:count]
+            offs = None if fixed else offs[:count + 1]
+        self.take_into(batch, kept, rows, offs, stream)
+        self.device_status(stream)
+        out = RowBatch(rows[:total], offs, count, self.schema_hash)
+        return (out, kept) if return_indices else out
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""

@@ -39,6 +39,8 @@
  *                           setNotNullAt (ordinal) over a batch, for the selected ordinals only
  *                           (FMT/row/binary/UnsafeTrait.java:203-266,
  *                            FMT/row/binary/BinaryRow.java:130-150)
+ *   fury_row_take /         BinaryRow.copy() over a batch, for the selected rows only: a row's bytes,
+ *   fury_row_filter         unchanged, at a new position (FMT/row/binary/BinaryRow.java:173-179)
  *   fury_rows_to_arrow      ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -272,6 +274,55 @@ int fury_row_project_measure(const fury_schema* schema, const int32_t* fields, i
 int fury_row_update(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
                     void* rows, const int64_t* row_offsets, int64_t nrows,
                     const fury_column* columns, const uint8_t* row_mask, void* stream);
+
+/* Row selection -- BinaryRow.copy() over a batch (FMT/row/binary/BinaryRow.java:173-179:
+ * buffer.copyTo(baseOffset, copyBuf, 0, sizeInBytes)).  Every (offset << 32) | size slot of a row is
+ * relative to the row's own base, so a selected row is its bytes, unchanged, at a new position: only
+ * row_offsets and bytes are used, and `schema` may be anything the library creates (flat, wide,
+ * nested, a collection schema).
+ *
+ * fury_row_take: output row j = the bytes of source row indices[j], j in [0, num_selected).
+ * `indices` is device int64 in any order, repeats allowed, num_selected may exceed nrows.
+ * out_offsets[0..num_selected] (device) receives the exclusive scan of the selected rows' sizes;
+ * out_offsets[num_selected] is the number of bytes the output needs.  Capacity as in
+ * fury_row_encode_measured: output bytes at or past out_capacity are never written while out_offsets
+ * is always complete, so the caller can grow the buffer and call again.  out_rows == NULL is the
+ * measure form: only out_offsets is written (out_capacity is ignored).
+ * is_fixed schemas: row_offsets may be NULL (a non-NULL one is ignored, as in fury_row_project),
+ * output row j sits at j * fixed_size, out_offsets may be NULL (when given it is filled with
+ * j * fixed_size), and out_rows != NULL with out_capacity < num_selected * fixed_size returns
+ * FURY_ERR_CAPACITY before any device work.
+ *
+ * fury_row_filter: keeps the rows whose row_mask bit is 1, in row order.  row_mask is LSB-first and
+ * READ as 32-bit words: 4-byte aligned and readable to a multiple of 4 bytes; bits at or past nrows
+ * in the last word are ignored.  *out_count (device int64, required) receives the number of rows
+ * kept; the host never reads it.  out_offsets needs nrows + 1 entries: entries [0, count] are the
+ * scan, entries (count, nrows] repeat out_offsets[count], so any prefix of at least count + 1 entries
+ * is a valid offsets array and the buffer's contents are deterministic.  out_indices (optional,
+ * nrows entries) receives the source row numbers kept in [0, count) and -1 in [count, nrows): use it
+ * to gather side columns.  Capacity and the measure form as for take.  is_fixed schemas: row_offsets
+ * and out_offsets may be NULL (out_offsets[j], when given, = min(j, count) * fixed_size); the count
+ * is not known on the host, so out_rows != NULL with out_capacity < nrows * fixed_size returns
+ * FURY_ERR_CAPACITY before any device work (out_rows == NULL: no capacity check).
+ *
+ * Bounds (both calls): a source row i is copied only when i is in [0, nrows), its extent
+ * [row_offsets[i], row_offsets[i + 1]) lies inside [0, row_offsets[nrows]), and the extent starts at a
+ * multiple of 8 with a non-negative size that is a multiple of 8.  Otherwise the output row has size
+ * 0 (is_fixed schemas, where only the index can fail: its fixed_size bytes are written as zeros) and
+ * FURY_ERR_OUT_OF_BOUNDS is reported on `stream` (fury_device_status), naming the output position j
+ * for take and the source row for filter.  Nothing outside the source batch is read and nothing
+ * outside [out_rows, out_rows + min(out_capacity, bytes needed)) is written.
+ * `rows` and `out_rows` are 8-byte aligned and must not overlap: overlapping buffers give unspecified
+ * contents, never an access outside the two buffers.  num_selected == 0 (take) / nrows == 0 (filter)
+ * still writes out_offsets[0] = 0 (when given) and *out_count = 0.  Both calls are asynchronous on
+ * `stream` with no host synchronisation; argument errors are returned before any device work. */
+int fury_row_take(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
+                  int64_t nrows, const int64_t* indices, int64_t num_selected,
+                  void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+int fury_row_filter(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
+                    int64_t nrows, const uint8_t* row_mask,
+                    void* out_rows, int64_t out_capacity, int64_t* out_offsets,
+                    int64_t* out_count, int64_t* out_indices, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
