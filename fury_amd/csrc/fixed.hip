@@ -519,8 +519,10 @@ int32_t tail_tiles_of(const FixedArgs& a, int R) {
 }  // namespace
 
 // Kernel choice (round-1/2 A/B sweeps, profiles/r01_ab_fixed*.json, r02_host_direct*.json; the
-// measured-slower pipelined persistent kernels, padded LDS rows, deep encode gather, pair-mode
-// encode and XCD-contiguous tile order were removed in round 3):
+// measured-slower pipelined persistent kernels, padded LDS rows and XCD-contiguous tile order were
+// removed in round 3; the pair-mode encode and the deeper encode gathers are still here, selected
+// by tuning fixed_enc, and tests/test_variants_gpu.py holds every selectable instance to the
+// oracle's bytes):
 //   fast path (8-byte columns, no validity): non-temporal loads + stores, except the row stores
 //     of the encode's tail window (store_tile, tuning fixed_enc_tail_kib); the encode gathers 16
 //     column loads per lane (round 6: 1.7 % faster than 8 on this ROCm; tuning fixed_enc); the decode keeps the whole tile in flight (16 loads per lane) and

@@ -233,13 +233,15 @@ def test_var_decode_lookback_help_bit_exact(oracle, dev):
     """The variable-length decodes number tiles by blockIdx and let a look-back compute a silent
     predecessor's aggregate from its rows (look_back_help).  Tuning "lookback_help" makes every
     look-back help at once -- the path a late-dispatched predecessor takes -- and the results must
-    still be the oracle's columns, for the register-staged (<= 16 fields) and the 17-256-field
-    kernels."""
+    still be the oracle's columns, for the register-staged kernels (<= 16 fields).  The 33- and
+    17-field legs run with the default var_wide 1, so they run the wide tiles' count and write
+    passes (wide.hip), which have no look-back; the 17-256-field look-back kernel
+    (decode_var_kernel, var_wide 0) is in tests/test_variants_gpu.py::test_var_wide."""
     from fury_amd import _native as N
     assert N.lib().fury_set_tuning(b"lookback_help", 1) == 0
     try:
         _roundtrips_var(oracle, dev, 32768)
-        for ncols, n in ((33, 2049), (17, 20_001)):    # the 17-256-field kernel (decode_var_kernel)
+        for ncols, n in ((33, 2049), (17, 20_001)):    # 17-256 fields: the wide tiles (var_wide 1)
             fields = _wide_fields(ncols)
             host = gen_columns("wide", fields, n, seed=ncols, null_pct=10, str_max=40, list_max=8)
             _roundtrip(oracle, None, n, dev, fields=fields, cols=host)

@@ -61,7 +61,7 @@ def _check(oracle, dev, schema, n, misalign=None):
     fields, host, want, ref = _reference(oracle, schema, n)
     enc = Encoders.bean(fields, device=dev)
     dcols = [column_to_device(c, dev) for c in host]
-    fast = all(f.type_id == T.INT64 and not f.nullable for f in fields)
+    fast = all(T.type_width(f.type_id) == 8 and not f.nullable for f in fields)
     saved = _lib().fury_get_tuning(KEY)
     try:
         for tail in TAILS:
