@@ -1205,6 +1205,56 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
   return launch_filter(a, row_mask, out_count, out_indices, hs);
 }
 
+// Nested values as batches (extract.hip): getStruct / getArray / getMap over a batch.  The path is
+// resolved on the host (schema.cpp); the per-level widths travel in the argument block.
+int fury_row_extract(const fury_schema* s, const int32_t* path, int32_t path_len, const void* rows,
+                     const int64_t* row_offsets, int64_t nrows, void* out_rows,
+                     int64_t out_capacity, int64_t* out_offsets, int64_t* out_count,
+                     int64_t* out_indices, uint8_t* out_validity, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_extract");
+  ExtractPath p;
+  int st = resolve_extract_path(s, path, path_len, f, &p);
+  if (st) return st;
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
+  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
+  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
+  if (misaligned(row_offsets, 8) || misaligned(out_offsets, 8) || misaligned(out_count, 8) ||
+      misaligned(out_indices, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": row_offsets / out_offsets / out_count / out_indices must be 8-byte aligned");
+  if (misaligned(out_validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_validity must be 4-byte aligned");
+  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  st = take_device_error(hs);
+  if (st) return st;
+  ExtractArgs a{};
+  a.rows = static_cast<const uint8_t*>(rows);
+  a.row_offsets = row_offsets;
+  a.nrows = nrows;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  a.out_count = out_count;
+  a.out_indices = out_indices;
+  a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
+  a.nlevels = path_len;
+  a.min_size = p.min_size;
+  a.exact = p.exact;
+  for (int32_t k = 0; k < path_len; k++) {
+    a.nfields[k] = p.nfields[k];
+    a.slot[k] = path[k];
+  }
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_extract(a, hs);
+}
+
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,
                         int64_t nrows, int64_t* node_entries, int64_t* node_bytes,
                         fury_decode_plan** plan, void* stream) {

@@ -89,6 +89,18 @@ namespace fury {
 int set_error(int status, const std::string& msg);
 int check_hip(int hip_status, const char* what);
 
+// A path of struct slots resolved against a row schema (schema.cpp; fury_schema_child and
+// fury_row_extract share it, rules and messages in include/fury_row.h).
+struct ExtractPath {
+  const OwnedField* end = nullptr;    // the STRUCT / LIST / MAP field the path reaches
+  std::vector<int32_t> nfields;       // per level: fields of the struct whose slot is followed
+  int32_t min_size = 0;               // STRUCT: fixed_size of a row of its fields; LIST / MAP: 8
+  int32_t exact = 0;                  // STRUCT whose fields are all fixed-width (is_fixed)
+};
+// `f`: the calling entry point's name, the prefix of every message.
+int resolve_extract_path(const fury_schema* s, const int32_t* path, int32_t path_len,
+                         const std::string& f, ExtractPath* out);
+
 inline int32_t bitmap_bytes(int64_t n) { return static_cast<int32_t>(((n + 63) / 64) * 8); }
 inline int64_t round8(int64_t n) { return (n + 7) & ~int64_t(7); }
 

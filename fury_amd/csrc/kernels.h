@@ -322,6 +322,36 @@ int launch_take(const TakeArgs& a, hipStream_t stream);
 int launch_filter(const TakeArgs& a, const uint8_t* row_mask, int64_t* out_count,
                   int64_t* out_indices, hipStream_t stream);
 
+// ---- nested values as batches: extract.hip -------------------------------------------------------
+// BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
+// row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like
+// launch_filter's outputs).  Level k of the path is a struct of nfields[k] fields whose slot slot[k]
+// is followed; the host resolves both from the schema (resolve_extract_path, schema.cpp).  Bounds =
+// "Decode bounds" above, per level: the struct's header [base, base + bitmap + 8 nfields) lies in
+// [0, total) at an 8-byte aligned base, the slot's offset and size are >= 0 and multiples of 8, the
+// value's span lies in [0, total) and is no shorter than `need` of the next level (the next struct's
+// header; the last value: min_size, and exactly min_size when `exact`).  A value that fails is null
+// and raises kErrBounds with its source row.  Asynchronous on `stream`.
+struct ExtractArgs {
+  const uint8_t* rows;
+  const int64_t* row_offsets;
+  int64_t nrows;
+  uint8_t* out;                       // NULL: the measure form
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries
+  int64_t* out_count;
+  int64_t* out_indices;               // optional, nrows entries
+  uint32_t* out_validity;             // optional, (nrows + 31) / 32 words
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t nlevels;                    // 1 .. kMaxNestLevels
+  int32_t min_size;                   // STRUCT: the child's fixed_size; LIST / MAP: 8
+  int32_t exact;                      // an is_fixed child struct: size == min_size
+  int32_t pad_;
+  int32_t nfields[64];                // kMaxNestLevels
+  int32_t slot[64];
+};
+int launch_extract(const ExtractArgs& a, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

@@ -143,6 +143,87 @@ static FieldPlan plan_field(const OwnedField& f, std::string* why) {
   return p;
 }
 
+static const char* type_name(int32_t t) {
+  switch (t) {
+    case FURY_TYPE_STRUCT: return "STRUCT";
+    case FURY_TYPE_LIST: return "LIST";
+    case FURY_TYPE_MAP: return "MAP";
+    case FURY_TYPE_STRING: return "STRING";
+    case FURY_TYPE_BINARY: return "BINARY";
+    case FURY_TYPE_DECIMAL: return "DECIMAL";
+    default: return "scalar";
+  }
+}
+
+int resolve_extract_path(const fury_schema* s, const int32_t* path, int32_t path_len,
+                         const std::string& f, ExtractPath* out) {
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (!path) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": path is null");
+  if (path_len < 1 || path_len > 64)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": path_len " + std::to_string(path_len) + " is not in [1, 64]");
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a collection schema has no struct fields to follow (its entries are "
+                         "arrays / maps, not rows)");
+  *out = ExtractPath{};
+  const std::vector<OwnedField>* level = &s->fields;
+  for (int32_t k = 0; k < path_len; k++) {
+    const int32_t n = static_cast<int32_t>(level->size());
+    if (path[k] < 0 || path[k] >= n)
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": path[" + std::to_string(k) + "] = " + std::to_string(path[k]) +
+                           " is not a slot of a struct of " + std::to_string(n) + " fields");
+    const OwnedField& fld = (*level)[path[k]];
+    const std::string who = "path[" + std::to_string(k) + "] (" + fld.name + ", " +
+                            type_name(fld.type_id) + ")";
+    out->nfields.push_back(n);
+    if (k + 1 < path_len) {
+      if (fld.type_id != FURY_TYPE_STRUCT)
+        return set_error(FURY_ERR_UNSUPPORTED,
+                         f + ": " + who + " is not a STRUCT: only struct slots can be followed");
+      level = &fld.children;
+      continue;
+    }
+    if (fld.type_id != FURY_TYPE_STRUCT && fld.type_id != FURY_TYPE_LIST &&
+        fld.type_id != FURY_TYPE_MAP)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + " is not a STRUCT, LIST or MAP: read it with "
+                           "fury_row_project");
+    out->end = &fld;
+    if (fld.type_id == FURY_TYPE_STRUCT) {
+      const int32_t m = static_cast<int32_t>(fld.children.size());
+      out->min_size = bitmap_bytes(m) + 8 * m;
+      out->exact = 1;
+      for (const auto& c : fld.children)
+        if (type_width(c.type_id) < 0) out->exact = 0;
+    } else {
+      out->min_size = 8;              // [int64 numElements] / [int64 keyArrayBytes]
+    }
+  }
+  return FURY_OK;
+}
+
+// The fury_field tree of OwnedFields (names point into them); `keep` owns the child arrays.
+static void c_fields(const std::vector<OwnedField>& in, std::vector<fury_field>* out,
+                     std::vector<std::vector<fury_field>>* keep) {
+  out->resize(in.size());
+  for (size_t i = 0; i < in.size(); i++) {
+    fury_field& o = (*out)[i];
+    o.name = in[i].name.c_str();
+    o.type_id = in[i].type_id;
+    o.nullable = in[i].nullable;
+    o.num_children = static_cast<int32_t>(in[i].children.size());
+    o.children = nullptr;
+    if (!in[i].children.empty()) {
+      std::vector<fury_field> kids;
+      c_fields(in[i].children, &kids, keep);
+      keep->push_back(std::move(kids));       // moving a vector keeps its buffer
+      o.children = keep->back().data();
+    }
+  }
+}
+
 }  // namespace fury
 
 using namespace fury;
@@ -323,6 +404,25 @@ int fury_collection_schema_create(const fury_field* field, fury_schema** out) {
   }
   *out = s;
   return FURY_OK;
+}
+
+int fury_schema_child(const fury_schema* s, const int32_t* path, int32_t path_len,
+                      fury_schema** out) {
+  const std::string f("fury_schema_child");
+  if (!out) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out is null");
+  *out = nullptr;
+  ExtractPath p;
+  int st = resolve_extract_path(s, path, path_len, f, &p);
+  if (st) return st;
+  std::vector<fury_field> top;
+  std::vector<std::vector<fury_field>> keep;
+  if (p.end->type_id == FURY_TYPE_STRUCT) {
+    c_fields(p.end->children, &top, &keep);
+    return fury_schema_create(top.data(), static_cast<int32_t>(top.size()), out);
+  }
+  const std::vector<OwnedField> one{*p.end};          // lives until the schema has copied it
+  c_fields(one, &top, &keep);
+  return fury_collection_schema_create(top.data(), out);
 }
 
 int32_t fury_schema_num_nodes(const fury_schema* s) {

@@ -859,6 +859,117 @@ class RowEncoder:
         out = RowBatch(rows[:total], offs, count, self.schema_hash)
         return (out, kept) if return_indices else out
 
+    # -- nested values as batches (BinaryRow.getStruct / getArray / getMap over a batch) ----------
+    def _path(self, path) -> List[int]:
+        """Slot indices of ``path``: field names or slot indices from the top level down through
+        STRUCT fields; a single name or index is a path of one."""
+        if isinstance(path, (str, int)):
+            path = [path]
+        fields, out = self._schema.fields, []
+        for x in path:
+            if isinstance(x, str):
+                names = {f.name: k for k, f in enumerate(fields)}
+                if x not in names:
+                    raise IllegalArgumentException(
+                        f"no field named {x!r} at path position {len(out)} in {self._schema}")
+                x = names[x]
+            k = int(x)
+            out.append(k)
+            node = fields[k] if 0 <= k < len(fields) else None
+            fields = node.children if node is not None and node.type_id == STRUCT else ()
+        return out
+
+    def child_encoder(self, path):
+        """The encoder of the nested field ``path`` reaches (see ``_path``), on this encoder's
+        device and cached per path: a ``RowEncoder`` of a STRUCT's fields, the ``ArrayEncoder`` of
+        a LIST field, the ``MapEncoder`` of a MAP field -- the codec of what ``extract`` returns."""
+        idx = self._path(path)
+        cache = self.__dict__.setdefault("_children", {})
+        enc = cache.get(tuple(idx))
+        if enc is None:
+            sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+            h = ctypes.c_void_p()              # the library checks the path: its rules, its messages
+            _check(N.lib().fury_schema_child(self._schema.handle, sel, len(idx), ctypes.byref(h)))
+            N.lib().fury_schema_destroy(h)
+            fields = self._schema.fields
+            for k in idx:
+                node, fields = fields[k], fields[k].children
+            enc = (RowEncoder(node.children, self.device) if node.type_id == STRUCT else
+                   ArrayEncoder(node, self.device) if node.type_id == LIST else
+                   MapEncoder(node, self.device))
+            cache[tuple(idx)] = enc
+        return enc
+
+    def _extract_args(self, batch: RowBatch, path, out_rows, out_offsets, out_count, out_indices,
+                      out_validity, stream, keep: list):
+        self._check_hash(batch)
+        idx = self._path(path)
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        return (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets), _ptr(out_count),
+                _ptr(out_indices), _ptr(out_validity), _stream_handle(stream))
+
+    def extract_into(self, batch: RowBatch, path, out_rows: Optional[torch.Tensor],
+                     out_offsets: torch.Tensor, out_count: torch.Tensor,
+                     out_indices: Optional[torch.Tensor] = None,
+                     out_validity: Optional[torch.Tensor] = None, stream=None) -> None:
+        """The value of the nested field ``path`` (see ``_path``; a STRUCT, LIST or MAP) of every
+        row of ``batch``, packed in row order into the preallocated ``out_rows`` as a batch of
+        ``child_encoder(path)``: one call, no host synchronisation.  Rows where the field (or a
+        struct on the way to it) is null produce no entry: ``out_count`` (int64[1]) receives the
+        number of entries, ``out_offsets`` (int64, nrows + 1 entries) their offsets -- entries past
+        the count repeat the total --, ``out_indices`` (optional, int64, nrows entries) their source
+        rows, -1 past the count, and ``out_validity`` (optional, uint8, whole 32-bit words) the Arrow
+        bitmap of the rows that produced one.  Capacity and ``out_rows=None`` as in ``take_into``; a
+        malformed value counts as null and is reported by ``device_status(stream)``."""
+        keep: list = []
+        _check(N.lib().fury_row_extract(*self._extract_args(
+            batch, path, out_rows, out_offsets, out_count, out_indices, out_validity, stream, keep)))
+
+    def bind_extract(self, batch: RowBatch, path, out_rows: Optional[torch.Tensor],
+                     out_offsets: torch.Tensor, out_count: torch.Tensor,
+                     out_indices: Optional[torch.Tensor] = None,
+                     out_validity: Optional[torch.Tensor] = None, stream=None):
+        """``extract_into`` bound like ``bind_take``: path and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_extract
+        args = self._extract_args(batch, path, out_rows, out_offsets, out_count, out_indices,
+                                  out_validity, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_rows, out_offsets, out_count, out_indices, out_validity, self,
+                     self._schema)
+        return call
+
+    def extract(self, batch: RowBatch, path, stream=None, return_indices: bool = False):
+        """``(values, validity)`` of the nested field ``path``: the non-null values as a new batch
+        of ``child_encoder(path)`` (its ``schema_hash``; 0 for a LIST or MAP) and the Arrow bitmap
+        (uint8, LSB-first) of the rows that have one; with ``return_indices`` also their row
+        numbers.  The values are located and measured on the device, count and byte total come back
+        in one host read, then they are copied."""
+        self._check_hash(batch)
+        idx = self._path(path)
+        child = self.child_encoder(idx)
+        n = batch.nrows
+        with _on(stream):
+            head = torch.empty(2, dtype=torch.int64, device=self.device)      # count, total
+            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            src = (torch.empty(max(n, 1), dtype=torch.int64, device=self.device)[:n]
+                   if return_indices else None)
+            valid = torch.zeros(((n + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
+            self.extract_into(batch, idx, None, offs, head[:1], None, None, stream)
+            head[1:] = offs[n:]
+            count, total = (int(x) for x in head.cpu())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.extract_into(batch, idx, rows, offs, head[:1], src if n else None,
+                          valid if n else None, stream)
+        self.device_status(stream)
+        out = RowBatch(rows[:total], offs[:count + 1], count, child.schema_hash)
+        valid = valid[:(n + 7) // 8]
+        return (out, valid, src[:count]) if return_indices else (out, valid)
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""

@@ -41,6 +41,11 @@
  *                            FMT/row/binary/BinaryRow.java:130-150)
  *   fury_row_take /         BinaryRow.copy() over a batch, for the selected rows only: a row's bytes,
  *   fury_row_filter         unchanged, at a new position (FMT/row/binary/BinaryRow.java:173-179)
+ *   fury_row_extract        BinaryRow.getStruct / getArray / getMap (ordinal) over a batch, along a path
+ *                           of struct ordinals: the nested row / BinaryArray / BinaryMap of every row
+ *                           as a batch of the child schema (fury_schema_child)
+ *                           (FMT/row/binary/UnsafeTrait.java:160-197,
+ *                            FMT/row/binary/BinaryMap.java:62-77)
  *   fury_rows_to_arrow      ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -323,6 +328,62 @@ int fury_row_filter(const fury_schema* schema, const void* rows, const int64_t* 
                     int64_t nrows, const uint8_t* row_mask,
                     void* out_rows, int64_t out_capacity, int64_t* out_offsets,
                     int64_t* out_count, int64_t* out_indices, void* stream);
+
+/* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
+ * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
+ * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
+ * row, array or map addresses its variable-length section relative to its own base, so the bytes the
+ * slot points at are, unchanged, a complete row of the child schema / a complete top-level
+ * BinaryArray (what ArrayEncoder.toArray writes) / a complete BinaryMap [int64 keyArrayBytes][keys]
+ * [values] (what MapEncoder.toMap writes).  fury_row_extract packs that value of every row into a new
+ * batch, which every other entry point takes with the schema fury_schema_child returns:
+ * a.b.name of a bean is extract {a, b} followed by fury_row_project of name.
+ *
+ * Path (both functions, same rules, each message prefixed with the function's name): path[0] is a
+ * top-level slot of `schema`, path[k] a slot of the STRUCT reached by path[0..k); every node but the
+ * last is a STRUCT, the last a STRUCT, LIST or MAP; 1 <= path_len <= 64 (the schema depth limit).
+ * A null path, path_len out of range or a slot index out of range returns FURY_ERR_INVALID_ARGUMENT;
+ * a scalar / STRING / BINARY / DECIMAL end node (use fury_row_project), a non-STRUCT node inside the
+ * path or a collection schema as `schema` returns FURY_ERR_UNSUPPORTED.
+ *
+ * fury_schema_child: the schema of the node the path reaches -- STRUCT: a row schema of its fields
+ * (info and hash equal fury_schema_create of those fields); LIST / MAP: the collection schema of that
+ * field (as fury_collection_schema_create).  The caller destroys it.  Host only.
+ *
+ * fury_row_extract, per row r with total = row_offsets[nrows] and B_0 = row_offsets[r]; level k is a
+ * struct of n_k fields with a bitmap of bm_k = ((n_k + 63) / 64) * 8 bytes:
+ *   1. the header [B_k, B_k + bm_k + 8 n_k) must lie in [0, total) and B_0 must be a multiple of 8
+ *      (as take requires of a row), else the value fails;
+ *   2. bit path[k] of the bitmap at B_k set: the value is null -- no error, nothing further is read;
+ *   3. slot = the int64 at B_k + bm_k + 8 path[k], off = (int32)(slot >> 32), size = (int32)slot as
+ *      UnsafeTrait reads them; the value spans [B_k + off, B_k + off + size) and B_{k+1} = B_k + off;
+ *   4. the value fails unless off >= 0, size >= 0, both are multiples of 8 (rows, arrays and maps are
+ *      8-byte padded by every writer), the span lies in [0, total), an intermediate struct has size >=
+ *      bm_{k+1} + 8 n_{k+1}, a final STRUCT has size >= the child's fixed_size (== fixed_size when the
+ *      child is_fixed, so that the packed output can be indexed as j * fixed_size) and a final LIST /
+ *      MAP has size >= 8.
+ * A value that fails is treated as null and FURY_ERR_OUT_OF_BOUNDS is reported on `stream`
+ * (fury_device_status), naming source row r -- fury_row_project's "decodes as null and is reported".
+ * Nothing outside [rows, rows + total) is read; validating the extracted bytes any deeper belongs to
+ * whatever decodes them.
+ * Outputs are compact, in row order, shaped like fury_row_filter's: *out_count (device int64,
+ * required, never read by the host) = the number of non-null values; out_offsets (required, nrows + 1
+ * entries): entries [0, count] are the exclusive scan of the sizes, entries (count, nrows] repeat
+ * out_offsets[count]; out_indices (optional, nrows entries): the source row of each entry, -1 past the
+ * count; out_validity (optional): an Arrow bitmap, LSB-first, bit r = 1: row r produced an entry,
+ * WRITTEN as whole 32-bit words -- 4-byte aligned, (nrows + 31) / 32 words, bits at or past nrows 0;
+ * out_rows: the values back to back, capacity and the measure form (out_rows == NULL) exactly as
+ * fury_row_take, 8-byte aligned, not overlapping `rows`.  row_offsets is required (a schema with a
+ * nested field is never is_fixed).  nrows == 0 writes *out_count = 0 and out_offsets[0] = 0.
+ * Asynchronous on `stream`, no host synchronisation; argument errors are returned before any device
+ * work, a pending device error of the stream first, as in the other entry points. */
+int fury_schema_child(const fury_schema* schema, const int32_t* path, int32_t path_len,
+                      fury_schema** out);
+int fury_row_extract(const fury_schema* schema, const int32_t* path, int32_t path_len,
+                     const void* rows, const int64_t* row_offsets, int64_t nrows,
+                     void* out_rows, int64_t out_capacity, int64_t* out_offsets,
+                     int64_t* out_count, int64_t* out_indices, uint8_t* out_validity,
+                     void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
