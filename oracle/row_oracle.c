@@ -6,8 +6,9 @@
  * Parity pinning: the reference's own known answers (ArrayEncoderTest lengths 224/1576/10824,
  * the C++ RowTest ToString answer, TypeInferenceTest order) and schema hashes produced by the
  * reference's python/pyfury/format/infer.py::compute_schema_hash, all under tests/golden/
- * (see DESIGN.md "Oracle").  The Java reference cannot be built here (no JDK) and the C++
- * sibling needs absl for its logging TU, so neither is executed.
+ * (see DESIGN.md "Oracle").  The Java reference cannot be built here (no JDK); the C++ sibling's
+ * row writer / reader is built by oracle/ref_cpp/ (with a stand-in for its absl-based logging TU)
+ * and compared with this file byte for byte by tests/test_reference_cpp.py.
  *
  * Every function names the reference file:line it restates.  Paths:
  *   FMT  = java/fury-format/src/main/java/org/apache/fury/format

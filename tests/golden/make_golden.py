@@ -13,6 +13,10 @@
 3. *.npz — seeded input columns + expected rows/offsets produced by the oracle restatement
    (oracle/row_oracle.c); regression fixtures for the device path (np.load allow_pickle=False).
 
+The *.npz files above are this project's own reading of the format, checked against itself.  The
+set that is NOT produced by our restatement is tests/golden/ref_cpp/ (make_ref_golden.py beside
+this file): its rows were written by the reference's own C++ row writer.
+
 Nothing here ships to, or is read on, the GPU box except the generated data files.
 """
 from __future__ import annotations
