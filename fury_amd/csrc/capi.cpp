@@ -1255,6 +1255,80 @@ int fury_row_extract(const fury_schema* s, const int32_t* path, int32_t path_len
   return launch_extract(a, hs);
 }
 
+// List and map elements as batches (explode.hip): BinaryArray.getStruct / getArray / getMap and
+// BinaryMap.keyArray / valueArray over a batch.  Path, side and element type are resolved on the host
+// (schema.cpp).
+int fury_row_explode(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
+                     const void* rows, const int64_t* row_offsets, int64_t nrows,
+                     int64_t* out_list_offsets, uint8_t* out_entry_validity, int64_t elem_capacity,
+                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, int64_t* out_count,
+                     int64_t* out_parents, int32_t* out_ordinals, uint8_t* out_validity,
+                     void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_explode");
+  ExplodePath p;
+  int st = resolve_explode_path(s, path, path_len, side, f, &p);
+  if (st) return st;
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
+  if (!out_list_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_list_offsets is null");
+  if (misaligned(row_offsets, 8) || misaligned(out_list_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": row_offsets / out_list_offsets must be 8-byte aligned");
+  if (misaligned(out_entry_validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_entry_validity must be 4-byte aligned");
+  if (!out_offsets) {                 // the count form
+    if (out_rows || out_count || out_parents || out_ordinals || out_validity)
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": out_offsets is null (the count form): out_rows, out_count, out_parents, "
+                           "out_ordinals and out_validity must be null too");
+  } else {
+    if (elem_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": elem_capacity < 0");
+    if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+    if (misaligned(out_rows, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+    if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
+    if (misaligned(out_offsets, 8) || misaligned(out_count, 8) || misaligned(out_parents, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": out_offsets / out_count / out_parents must be 8-byte aligned");
+    if (misaligned(out_ordinals, 4) || misaligned(out_validity, 4))
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": out_ordinals / out_validity must be 4-byte aligned");
+  }
+  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  st = take_device_error(hs);
+  if (st) return st;
+  ExplodeArgs a{};
+  a.rows = static_cast<const uint8_t*>(rows);
+  a.row_offsets = row_offsets;
+  a.nrows = nrows;
+  a.out_list_offsets = out_list_offsets;
+  a.out_entry_validity = reinterpret_cast<uint32_t*>(out_entry_validity);
+  a.elem_cap = out_offsets ? elem_capacity : 0;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  a.out_count = out_count;
+  a.out_parents = out_parents;
+  a.out_ordinals = out_ordinals;
+  a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
+  a.nlevels = s->root != 0 ? 0 : path_len;
+  a.min_size = 8;
+  a.exact = 0;
+  a.is_map = p.is_map;
+  a.side = side;
+  a.elem_min = p.elem_min;
+  a.elem_exact = p.elem_exact;
+  for (int32_t k = 0; k < a.nlevels; k++) {
+    a.nfields[k] = p.path.nfields[k];
+    a.slot[k] = path[k];
+  }
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_explode(a, hs);
+}
+
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,
                         int64_t nrows, int64_t* node_entries, int64_t* node_bytes,
                         fury_decode_plan** plan, void* stream) {

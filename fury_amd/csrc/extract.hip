@@ -24,23 +24,17 @@
 //              read from the compacted array.
 // Bounds ("Decode bounds" of kernels.h, per level; ExtractArgs): nothing outside [0, total) of the
 // rows buffer is read, the output is written only inside [0, min(capacity, needed)).
-#include "take_dev.h"
+#include "extract_dev.h"
 
 namespace fury {
 
 namespace {
 
-using v2l = __attribute__((ext_vector_type(2))) int64_t;
-
 static_assert(sizeof(ExtractArgs{}.nfields) / sizeof(int32_t) == kMaxNestLevels,
               "a path is as long as a schema is deep");
 
-__device__ __forceinline__ int32_t header_bytes(int32_t nfields) {
-  return (((nfields + 63) >> 6) << 3) + 8 * nfields;
-}
-
 // tc[t] / masks[t]: count and ballot of tile t (rows [64 t, 64 t + 64)); loc[r] = (source start,
-// size) of row r's value, written only when the row has one.
+// size) of row r's value, written only when the row has one.  The walk itself: extract_dev.h.
 __global__ __launch_bounds__(kTakeThreads) void extract_locate(ExtractArgs a,
                                                                int64_t* __restrict__ tc,
                                                                uint64_t* __restrict__ masks,
@@ -48,49 +42,13 @@ __global__ __launch_bounds__(kTakeThreads) void extract_locate(ExtractArgs a,
   const int64_t r = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
   const int64_t n = a.nrows;
   const int64_t total = gl(a.row_offsets)[n];
-  bool live = r < n, bad = false;
-  int64_t base = live ? gl(a.row_offsets)[r] : 0;
-  int64_t size = 0;
-  if (live && (base & 7)) {
-    bad = true;
-    live = false;
-  }
-  for (int k = 0; k < a.nlevels; k++) {             // wave-uniform: nfields / slot are scalar loads
-    const int32_t nf = a.nfields[k], sl = a.slot[k];
-    const int32_t bm = ((nf + 63) >> 6) << 3;
-    const bool last = k + 1 == a.nlevels;
-    const int32_t need = last ? a.min_size : header_bytes(a.nfields[k + 1]);
-    if (!live) continue;
-    live = false;
-    if (!span_ok(base, bm + 8 * nf, total)) {
-      bad = true;
-      continue;
-    }
-    const uint64_t word = gl(reinterpret_cast<const uint64_t*>(a.rows + base))[sl >> 6];
-    if ((word >> (sl & 63)) & 1) continue;          // null: nothing further of the row is read
-    const uint64_t s = gl(reinterpret_cast<const uint64_t*>(a.rows + base + bm))[sl];
-    const int32_t off = static_cast<int32_t>(s >> 32), len = static_cast<int32_t>(s);
-    if (off < 0 || len < 0 || ((off | len) & 7) || !span_ok(base + off, len, total) || len < need ||
-        (last && a.exact && len != need)) {
-      bad = true;
-      continue;
-    }
-    base += off;
-    size = len;
-    live = true;
-  }
+  int64_t base, size;
+  bool bad;
+  const bool live = walk_path(a, r, total, &base, &size, &bad);
   if (bad) raise_oob(a.err, r);
   const uint64_t m = __ballot(live);
   if (r >= n) return;
-  if ((threadIdx.x & 63) == 0) {
-    const int64_t t = r >> 6;
-    gl(tc)[t] = __popcll(m);
-    gl(masks)[t] = m;
-    if (a.out_validity) {
-      gl(a.out_validity)[2 * t] = static_cast<uint32_t>(m);
-      if (r + 32 < n) gl(a.out_validity)[2 * t + 1] = static_cast<uint32_t>(m >> 32);
-    }
-  }
+  if ((threadIdx.x & 63) == 0) put_tile(r >> 6, m, n, tc, masks, a.out_validity);
   if (live) gl(loc)[r] = v2l{base, size};
 }
 
@@ -103,21 +61,9 @@ __global__ __launch_bounds__(kTakeThreads) void extract_compact(const uint64_t* 
                                                                 int64_t* __restrict__ idx,
                                                                 int64_t* __restrict__ src,
                                                                 int64_t* __restrict__ oo) {
-  const int64_t r = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
-  if (r >= nrows) return;
-  const int lane = static_cast<int>(r & 63);
-  const uint64_t m = gl(masks)[r >> 6];
-  if ((m >> lane) & 1) {
-    const int64_t pos = gl(tc)[r >> 6] + __popcll(m & ((1ull << lane) - 1));
-    const v2l v = gl(loc)[r];
-    if (idx) gl(idx)[pos] = r;
-    if (src) gl(src)[pos] = v.x;
-    gl(oo)[pos] = v.y;
-  }
-  if (r >= *gl(count)) {              // the entries past the count: this lane's own position
-    if (idx) gl(idx)[r] = -1;
-    gl(oo)[r] = 0;
-  }
+  compact_entries(masks, loc, nrows, tc, count, src, oo,
+                  [=](int64_t pos, int64_t r) { if (idx) gl(idx)[pos] = r; },
+                  [=](int64_t r) { if (idx) gl(idx)[r] = -1; });
 }
 
 // n output rows at oo[0..n] (oo[n] = bytes needed); output row j = the bytes at src[j].

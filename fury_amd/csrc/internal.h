@@ -101,6 +101,19 @@ struct ExtractPath {
 int resolve_extract_path(const fury_schema* s, const int32_t* path, int32_t path_len,
                          const std::string& f, ExtractPath* out);
 
+// The array fury_schema_element / fury_row_explode work on (schema.cpp; rules and messages in
+// include/fury_row.h): the LIST / MAP a path reaches in a row schema, or the field of a collection
+// schema (path_len 0), and its key / element (side 0) or value (side 1) field.
+struct ExplodePath {
+  ExtractPath path;                   // row schema: the walk to the LIST / MAP; else empty
+  const OwnedField* elem = nullptr;   // the STRUCT / LIST / MAP element field of the chosen array
+  int32_t is_map = 0;
+  int32_t elem_min = 0;               // STRUCT: fixed_size of a row of its fields; LIST / MAP: 8
+  int32_t elem_exact = 0;             // STRUCT whose fields are all fixed-width (is_fixed)
+};
+int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
+                         const std::string& f, ExplodePath* out);
+
 inline int32_t bitmap_bytes(int64_t n) { return static_cast<int32_t>(((n + 63) / 64) * 8); }
 inline int64_t round8(int64_t n) { return (n + 7) & ~int64_t(7); }
 

@@ -352,6 +352,45 @@ struct ExtractArgs {
 };
 int launch_extract(const ExtractArgs& a, hipStream_t stream);
 
+// ---- list and map elements as batches: explode.hip -----------------------------------------------
+// BinaryArray.getStruct / getArray / getMap (ordinal) and BinaryMap.keyArray() / valueArray() over a
+// batch: the bytes every non-null element slot of the chosen array points at, unchanged, packed into
+// a new batch in (row, ordinal) order.  The array of row r is the LIST / MAP value the path reaches
+// (the members the walk reads are ExtractArgs', min_size = 8) or, for a collection schema (nlevels
+// 0), the batch entry itself; is_map / side pick the key or the value array of a BinaryMap.  Bounds =
+// "Decode bounds" above: the array's header and slot region [A, A + 8 + bitmap + 8 n) lies inside the
+// array's span, which lies in [0, total); an element's span is relative to A, its offset and size are
+// >= 0 and multiples of 8, it lies in [0, total) and is no shorter than elem_min (exactly elem_min
+// when elem_exact).  A row or element that fails is null and raises kErrBounds with the source row.
+// Elements at or past elem_cap are neither produced nor counted.  Asynchronous on `stream`.
+struct ExplodeArgs {
+  const uint8_t* rows;
+  const int64_t* row_offsets;
+  int64_t nrows;
+  int64_t* out_list_offsets;          // nrows + 1 entries: the Arrow list offsets of the column
+  uint32_t* out_entry_validity;       // optional, (nrows + 31) / 32 words
+  int64_t elem_cap;
+  uint8_t* out;                       // NULL: the measure form
+  int64_t cap;
+  int64_t* out_offsets;               // elem_cap + 1 entries; NULL: the count form
+  int64_t* out_count;
+  int64_t* out_parents;               // optional, elem_cap entries
+  int32_t* out_ordinals;              // optional, elem_cap entries
+  uint32_t* out_validity;             // optional, (elem_cap + 31) / 32 words
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t nlevels;                    // 0 (collection schema) .. kMaxNestLevels
+  int32_t min_size;                   // 8: the least LIST / MAP value
+  int32_t exact;                      // 0
+  int32_t is_map;                     // the value is a BinaryMap [int64 keyArrayBytes][keys][values]
+  int32_t side;                       // 0: the LIST / the key array; 1: the value array
+  int32_t elem_min;                   // STRUCT element: its fixed_size; LIST / MAP element: 8
+  int32_t elem_exact;                 // an is_fixed element struct: size == elem_min
+  int32_t pad_;
+  int32_t nfields[64];                // kMaxNestLevels
+  int32_t slot[64];
+};
+int launch_explode(const ExplodeArgs& a, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

@@ -204,6 +204,55 @@ int resolve_extract_path(const fury_schema* s, const int32_t* path, int32_t path
   return FURY_OK;
 }
 
+int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
+                         const std::string& f, ExplodePath* out) {
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  *out = ExplodePath{};
+  const OwnedField* coll;
+  if (s->root != 0) {
+    if (path_len != 0)
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": path_len " + std::to_string(path_len) + " with a collection schema: "
+                           "every entry is the array / map itself, path_len must be 0");
+    coll = &s->fields[0];
+  } else {
+    const int st = resolve_extract_path(s, path, path_len, f, &out->path);
+    if (st) return st;
+    coll = out->path.end;
+    if (coll->type_id == FURY_TYPE_STRUCT)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": path[" + std::to_string(path_len - 1) + "] (" + coll->name +
+                           ", STRUCT) is not a LIST or MAP: a struct has fields, not elements "
+                           "(read it with fury_row_extract)");
+  }
+  out->is_map = coll->type_id == FURY_TYPE_MAP;
+  if (side != 0 && side != 1)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": side " + std::to_string(side) + " is not 0 (LIST elements / MAP keys) "
+                         "or 1 (MAP values)");
+  if (side == 1 && !out->is_map)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": side 1 (MAP values) on the LIST " + coll->name);
+  const OwnedField& e = coll->children[side];
+  if (e.type_id != FURY_TYPE_STRUCT && e.type_id != FURY_TYPE_LIST && e.type_id != FURY_TYPE_MAP)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": the " + (out->is_map ? (side ? "values" : "keys") : "elements") + " of " +
+                         coll->name + " are " + type_name(e.type_id) + ", not STRUCT, LIST or MAP: "
+                         "such elements already decode as a flat child column through "
+                         "fury_decode_prepare / fury_row_project");
+  out->elem = &e;
+  if (e.type_id == FURY_TYPE_STRUCT) {
+    const int32_t m = static_cast<int32_t>(e.children.size());
+    out->elem_min = bitmap_bytes(m) + 8 * m;
+    out->elem_exact = 1;
+    for (const auto& c : e.children)
+      if (type_width(c.type_id) < 0) out->elem_exact = 0;
+  } else {
+    out->elem_min = 8;                // [int64 numElements] / [int64 keyArrayBytes]
+  }
+  return FURY_OK;
+}
+
 // The fury_field tree of OwnedFields (names point into them); `keep` owns the child arrays.
 static void c_fields(const std::vector<OwnedField>& in, std::vector<fury_field>* out,
                      std::vector<std::vector<fury_field>>* keep) {
@@ -421,6 +470,25 @@ int fury_schema_child(const fury_schema* s, const int32_t* path, int32_t path_le
     return fury_schema_create(top.data(), static_cast<int32_t>(top.size()), out);
   }
   const std::vector<OwnedField> one{*p.end};          // lives until the schema has copied it
+  c_fields(one, &top, &keep);
+  return fury_collection_schema_create(top.data(), out);
+}
+
+int fury_schema_element(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
+                        fury_schema** out) {
+  const std::string f("fury_schema_element");
+  if (!out) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out is null");
+  *out = nullptr;
+  ExplodePath p;
+  int st = resolve_explode_path(s, path, path_len, side, f, &p);
+  if (st) return st;
+  std::vector<fury_field> top;
+  std::vector<std::vector<fury_field>> keep;
+  if (p.elem->type_id == FURY_TYPE_STRUCT) {
+    c_fields(p.elem->children, &top, &keep);
+    return fury_schema_create(top.data(), static_cast<int32_t>(top.size()), out);
+  }
+  const std::vector<OwnedField> one{*p.elem};         // lives until the schema has copied it
   c_fields(one, &top, &keep);
   return fury_collection_schema_create(top.data(), out);
 }

@@ -1,6 +1,7 @@
 // take_dev.h -- the byte-balanced, output-parallel row copy shared by take.hip (fury_row_take /
-// fury_row_filter) and extract.hip (fury_row_extract).  Each includes it and instantiates copy_rows
-// with its own lookup of an output row's source start; the design is described in take.hip.
+// fury_row_filter), extract.hip (fury_row_extract) and explode.hip (fury_row_explode).  Each
+// includes it (the last two through extract_dev.h) and instantiates copy_rows with its own lookup
+// of an output row's source start; the design is described in take.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -970,6 +970,140 @@ class RowEncoder:
         valid = valid[:(n + 7) // 8]
         return (out, valid, src[:count]) if return_indices else (out, valid)
 
+    # -- list and map elements as batches (BinaryArray.getStruct / getArray / getMap over a batch) -
+    def _explode_sel(self, path, side):
+        """(slot indices of ``path``, the C ``side``): "elements" (a LIST) and "keys" (a MAP) are
+        side 0, "values" (a MAP) is side 1.  A collection encoder's own path is empty."""
+        sides = {"elements": 0, "keys": 0, "values": 1}
+        if side not in sides:
+            raise IllegalArgumentException(f"side {side!r} is not one of {sorted(sides)}")
+        return self._path(() if path is None else path), sides[side]
+
+    def element_encoder(self, path, side: str = "elements"):
+        """The encoder of the elements (``side`` "elements" of a LIST, "keys" / "values" of a MAP)
+        of the LIST or MAP field ``path`` reaches (see ``_path``), cached like ``child_encoder``: a
+        ``RowEncoder`` of a STRUCT element's fields, the ``ArrayEncoder`` / ``MapEncoder`` of a
+        LIST / MAP element -- the codec of what ``explode`` returns."""
+        idx, sd = self._explode_sel(path, side)
+        cache = self.__dict__.setdefault("_elements", {})
+        enc = cache.get((tuple(idx), sd))
+        if enc is None:
+            sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+            h = ctypes.c_void_p()              # the library checks path and side: its rules, its messages
+            _check(N.lib().fury_schema_element(self._schema.handle, sel, len(idx), sd,
+                                               ctypes.byref(h)))
+            N.lib().fury_schema_destroy(h)
+            fields = self._schema.fields
+            node = fields[0]                   # a collection schema: its one field
+            for k in idx:
+                node, fields = fields[k], fields[k].children
+            e = node.children[sd]
+            enc = (RowEncoder(e.children, self.device) if e.type_id == STRUCT else
+                   ArrayEncoder(e, self.device) if e.type_id == LIST else MapEncoder(e, self.device))
+            cache[(tuple(idx), sd)] = enc
+        return enc
+
+    def _explode_args(self, batch: RowBatch, path, side, out_list_offsets, out_entry_validity,
+                      out_rows, out_offsets, out_count, out_parents, out_ordinals, out_validity,
+                      elem_capacity, stream, keep: list):
+        self._check_hash(batch)
+        idx, sd = self._explode_sel(path, side)
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        if elem_capacity is None:
+            elem_capacity = 0 if out_offsets is None else out_offsets.numel() - 1
+        return (self._schema.handle, sel, len(idx), sd, _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _ptr(out_list_offsets), _ptr(out_entry_validity), int(elem_capacity),
+                _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets), _ptr(out_count),
+                _ptr(out_parents), _ptr(out_ordinals), _ptr(out_validity), _stream_handle(stream))
+
+    def explode_into(self, batch: RowBatch, path, out_list_offsets: torch.Tensor,
+                     out_entry_validity: Optional[torch.Tensor] = None,
+                     out_rows: Optional[torch.Tensor] = None,
+                     out_offsets: Optional[torch.Tensor] = None,
+                     out_count: Optional[torch.Tensor] = None,
+                     out_parents: Optional[torch.Tensor] = None,
+                     out_ordinals: Optional[torch.Tensor] = None,
+                     out_validity: Optional[torch.Tensor] = None, side: str = "elements",
+                     elem_capacity: Optional[int] = None, stream=None) -> None:
+        """The non-null elements of the LIST or MAP field ``path`` (``side``: see
+        ``element_encoder``) of every row of ``batch``, packed in (row, ordinal) order into the
+        preallocated ``out_rows`` as a batch of ``element_encoder(path, side)``: one call, no host
+        synchronisation.  ``out_list_offsets`` (int64, nrows + 1 entries) receives the Arrow list
+        offsets of the column -- its last entry is the element count E, nulls included --,
+        ``out_entry_validity`` (optional, uint8, whole 32-bit words) the bitmap of the rows that
+        have an array.  Per element, for at most ``elem_capacity`` elements (default: the entries
+        of ``out_offsets`` - 1): ``out_count`` (int64[1]) the number of entries, ``out_offsets``
+        (int64, elem_capacity + 1 entries) their offsets -- entries past the count repeat the total
+        --, ``out_parents`` (optional, int64) / ``out_ordinals`` (optional, int32) the source row
+        and the ordinal of each entry, -1 past the count, and ``out_validity`` (optional, uint8,
+        whole 32-bit words) the Arrow validity of the LIST's child.  ``out_offsets=None`` is the
+        count form: only the first two outputs.  Capacity and ``out_rows=None`` as in
+        ``take_into``; a malformed array or element counts as null and is reported by
+        ``device_status(stream)``."""
+        keep: list = []
+        _check(N.lib().fury_row_explode(*self._explode_args(
+            batch, path, side, out_list_offsets, out_entry_validity, out_rows, out_offsets,
+            out_count, out_parents, out_ordinals, out_validity, elem_capacity, stream, keep)))
+
+    def bind_explode(self, batch: RowBatch, path, out_list_offsets: torch.Tensor,
+                     out_entry_validity: Optional[torch.Tensor] = None,
+                     out_rows: Optional[torch.Tensor] = None,
+                     out_offsets: Optional[torch.Tensor] = None,
+                     out_count: Optional[torch.Tensor] = None,
+                     out_parents: Optional[torch.Tensor] = None,
+                     out_ordinals: Optional[torch.Tensor] = None,
+                     out_validity: Optional[torch.Tensor] = None, side: str = "elements",
+                     elem_capacity: Optional[int] = None, stream=None):
+        """``explode_into`` bound like ``bind_extract``: path and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_explode
+        args = self._explode_args(batch, path, side, out_list_offsets, out_entry_validity, out_rows,
+                                  out_offsets, out_count, out_parents, out_ordinals, out_validity,
+                                  elem_capacity, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_list_offsets, out_entry_validity, out_rows, out_offsets,
+                     out_count, out_parents, out_ordinals, out_validity, self, self._schema)
+        return call
+
+    def explode(self, batch: RowBatch, path, side: str = "elements", stream=None):
+        """``(elements, list_offsets, entry_validity, elem_validity, parents, ordinals)`` of the
+        LIST or MAP field ``path``: the non-null elements as a new batch of
+        ``element_encoder(path, side)``, the Arrow list offsets (int64, nrows + 1) and validity
+        (uint8, LSB-first) of the column, the Arrow validity of its child (one bit per element,
+        nulls included), and the source row (int64) and ordinal (int32) of every entry of
+        ``elements``.  The arrays are counted on the device (one host read of the element count),
+        the elements located and measured (one host read of entry count and byte total), then
+        copied."""
+        self._check_hash(batch)
+        idx, _ = self._explode_sel(path, side)
+        # RowEncoder.*: a collection encoder overrides these methods without the path
+        child = RowEncoder.element_encoder(self, idx, side)
+        n = batch.nrows
+        with _on(stream):
+            lo = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            ev = torch.zeros(((n + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
+            into = lambda *a: RowEncoder.explode_into(self, batch, idx, lo, ev if n else None, *a,  # noqa: E731
+                                                      side=side, stream=stream)
+            into()
+            E = int(lo[n].item())
+            head = torch.empty(2, dtype=torch.int64, device=self.device)      # count, total
+            offs = torch.empty(E + 1, dtype=torch.int64, device=self.device)
+            par = torch.empty(max(E, 1), dtype=torch.int64, device=self.device)[:E]
+            ords = torch.empty(max(E, 1), dtype=torch.int32, device=self.device)[:E]
+            valid = torch.zeros(((E + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
+            outs = (par if E else None, ords if E else None, valid if E else None)
+            into(None, offs, head[:1], *outs)
+            head[1:] = offs[E:]
+            count, total = (int(x) for x in head.cpu())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        into(rows, offs, head[:1], *outs)
+        self.device_status(stream)
+        out = RowBatch(rows[:total], offs[:count + 1], count, child.schema_hash)
+        return (out, lo, ev[:(n + 7) // 8], valid[:(E + 7) // 8], par[:count], ords[:count])
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""
@@ -1282,6 +1416,23 @@ class _CollectionEncoder(RowEncoder):
     def _bytes(self, values: list) -> bytes:
         b = self.encode_batch([self._column([values])], 1)
         return bytes(b.rows.cpu().numpy())
+
+    # -- the elements of every entry as a batch: RowEncoder's methods with the empty path ------------
+    def element_encoder(self, side: str = "elements"):
+        """The encoder of this collection's elements ("elements" of a list, "keys" / "values" of a
+        map): see ``RowEncoder.element_encoder``."""
+        return RowEncoder.element_encoder(self, (), side)
+
+    def explode_into(self, batch: RowBatch, out_list_offsets: torch.Tensor, *outs, **kw) -> None:
+        """``RowEncoder.explode_into`` without the path: every batch entry is the array / map."""
+        RowEncoder.explode_into(self, batch, (), out_list_offsets, *outs, **kw)
+
+    def bind_explode(self, batch: RowBatch, out_list_offsets: torch.Tensor, *outs, **kw):
+        return RowEncoder.bind_explode(self, batch, (), out_list_offsets, *outs, **kw)
+
+    def explode(self, batch: RowBatch, side: str = "elements", stream=None):
+        """``RowEncoder.explode`` without the path: the elements of every entry of ``batch``."""
+        return RowEncoder.explode(self, batch, (), side, stream)
 
     def encode_stream(self, values: list) -> bytes:
         """``encode(MemoryBuffer, T)``: [int32 size][bytes] (Encoders.java:372-386 / 575-590)."""

@@ -46,7 +46,12 @@
  *                           as a batch of the child schema (fury_schema_child)
  *                           (FMT/row/binary/UnsafeTrait.java:160-197,
  *                            FMT/row/binary/BinaryMap.java:62-77)
- *   fury_rows_to_arrow      ArrowWriter.write(row)* + finishAsRecordBatch
+ *   fury_row_explode        BinaryArray.getStruct / getArray / getMap (ordinal) and BinaryMap.keyArray /
+ *                           valueArray over a batch: the elements of a list or map field of every row
+ *                           as a batch of the element schema (fury_schema_element)
+ *                           (FMT/row/binary/BinaryArray.java:137-150,
+ *                            FMT/row/binary/BinaryMap.java:101-108)
+ *   fury_rows_to_arrow     ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
  *                           (FMT/vectorized/ArrowWriter.java:74-99)
@@ -383,6 +388,89 @@ int fury_row_extract(const fury_schema* schema, const int32_t* path, int32_t pat
                      const void* rows, const int64_t* row_offsets, int64_t nrows,
                      void* out_rows, int64_t out_capacity, int64_t* out_offsets,
                      int64_t* out_count, int64_t* out_indices, uint8_t* out_validity,
+                     void* stream);
+
+/* List and map elements as batches -- BinaryArray.getStruct / getArray / getMap (ordinal)
+ * (FMT/row/binary/BinaryArray.java:137-150, through UnsafeTrait.java:160-197) and BinaryMap.keyArray()
+ * / valueArray() (FMT/row/binary/BinaryMap.java:62-77,101-108) over a batch.  An element slot is
+ * (offset << 32) | size relative to the ARRAY's base, and a nested row, array or map addresses its
+ * variable-length section relative to its own base, so the bytes an element slot points at are,
+ * unchanged, a complete row of the element struct's schema / a complete BinaryArray / BinaryMap.
+ * fury_row_explode packs the non-null elements of every row's array into a new batch, which every
+ * other entry point takes with the schema fury_schema_element returns: orders[*].price is explode
+ * {orders} followed by fury_row_project of price.
+ *
+ * Which array (both functions, same rules, each message prefixed with the function's name):
+ *   - `schema` is a row schema: `path` follows fury_row_extract's rules and must end at a LIST or MAP
+ *     (a path ending at a STRUCT returns FURY_ERR_UNSUPPORTED: use fury_row_extract); or
+ *   - `schema` is a collection schema: path_len must be 0 (else FURY_ERR_INVALID_ARGUMENT), path may be
+ *     NULL, and every batch entry is the array / map itself -- what fury_row_extract or fury_row_encode
+ *     of a collection schema produced;
+ *   - side 0: the LIST's elements or the MAP's key array; side 1: the MAP's value array.  side 1 on a
+ *     LIST, or any other value, returns FURY_ERR_INVALID_ARGUMENT;
+ *   - the element type of the chosen array must be STRUCT, LIST or MAP; any other returns
+ *     FURY_ERR_UNSUPPORTED (such elements already decode as a flat child column through
+ *     fury_decode_prepare / fury_row_project).
+ *
+ * fury_schema_element: the schema of the output batch -- STRUCT element: a row schema of its fields
+ * (info and hash equal fury_schema_create of those fields); LIST / MAP element: the collection schema
+ * of the element field (as fury_collection_schema_create).  The caller destroys it.  Host only.
+ *
+ * fury_row_explode, per row r with total = row_offsets[nrows]:
+ *   1. the path is walked exactly as fury_row_extract's steps 1-4 walk it, giving the value's span
+ *      [V, V + size), size >= 8, or null, or a failure.  With a collection schema the span is the entry
+ *      [row_offsets[r], row_offsets[r + 1]): 8-byte aligned, size >= 8 and a multiple of 8, inside
+ *      [0, total), else the row fails;
+ *   2. MAP: kb = (int32) of the 8 bytes at V (BinaryMap.pointTo); the row fails unless kb >= 0,
+ *      kb % 8 == 0 and 8 + kb <= size.  The key array is [V + 8, V + 8 + kb), the value array
+ *      [V + 8 + kb, V + size); the chosen array [A, A + asz) needs asz >= 8.  The other side is never
+ *      read (key and value counts that differ are the full decode's error).  LIST: A = V, asz = size;
+ *   3. n = (int32) of the int64 at A (BinaryArray.pointTo); the row fails unless n >= 0 and
+ *      8 + ((n + 63) / 64) * 8 + 8 n <= asz, so that header and slots lie inside the array;
+ *   4. a row that is null or fails has 0 elements; a failure reports FURY_ERR_OUT_OF_BOUNDS on `stream`
+ *      (fury_device_status) naming row r;
+ *   5. out_list_offsets[0 .. nrows] (device, required) = the exclusive scan of n: the Arrow list
+ *      offsets of the column; E = out_list_offsets[nrows];
+ *   6. out_entry_validity (optional): bit r = 1: row r has a well-formed, non-null array; written as
+ *      whole 32-bit words like fury_row_extract's out_validity.
+ * Per element e = out_list_offsets[r] + i, i < n, e < elem_capacity: it is null (no entry, no error)
+ * when bit i of the bitmap at A + 8 is set; else off = (int32)(slot >> 32), size = (int32)slot of the
+ * slot at A + 8 + ((n + 63) / 64) * 8 + 8 i, and the element fails unless both are >= 0 and multiples
+ * of 8, [A + off, A + off + size) lies in [0, total), a STRUCT element has size >= the element
+ * schema's fixed_size (== fixed_size when it is_fixed) and a LIST / MAP element has size >= 8.  An
+ * element that fails is treated as null and FURY_ERR_OUT_OF_BOUNDS names row r.
+ * Outputs are shaped like fury_row_extract's, indexed by element instead of by row: *out_count = the
+ * entries produced; out_offsets: elem_capacity + 1 entries, [0, count] the exclusive scan of the
+ * sizes, (count, elem_capacity] repeating out_offsets[count]; out_parents (optional, elem_capacity
+ * int64): the source row of each entry, -1 past the count; out_ordinals (optional, elem_capacity
+ * int32): the entry's ordinal in its array, -1 past the count; out_validity (optional,
+ * (elem_capacity + 31) / 32 whole 32-bit words): bit e = 1: element e produced an entry, bits at or
+ * past min(E, elem_capacity) 0 -- the Arrow validity of the LIST's child; out_rows / out_capacity: the
+ * element values back to back, capacity and the measure form (out_rows == NULL) exactly as
+ * fury_row_take.
+ * Element capacity: elements at or past elem_capacity are neither produced nor counted, while
+ * out_list_offsets is always complete: a caller that sees out_list_offsets[nrows] > elem_capacity
+ * grows its buffers and calls again (the fury_row_encode_measured contract).  Every counted element
+ * owns an 8-byte slot inside its row's array, so E <= row_offsets[nrows] / 8 for every batch whose
+ * rows do not share bytes (every writer's output): elem_capacity = rows bytes / 8 is a bound the host
+ * knows without synchronising.  (Malformed slots may point two rows at the same array; E is then still
+ * exact and the capacity rule still holds.)
+ * The count form, out_offsets == NULL, writes only out_list_offsets and out_entry_validity: out_rows,
+ * out_count, out_parents, out_ordinals and out_validity must be NULL, elem_capacity is ignored.
+ * Otherwise as fury_row_extract: asynchronous on `stream` with no host synchronisation; a pending
+ * device error of the stream is returned first; argument errors (null / misaligned pointers,
+ * negative nrows, out_capacity or elem_capacity) are returned before any device work; nrows == 0
+ * writes out_list_offsets[0] = 0, *out_count = 0 and out_offsets[0] = 0; `rows` and `out_rows` must
+ * not overlap; nothing outside [rows, rows + total) is read and nothing outside the given output
+ * extents is written. */
+int fury_schema_element(const fury_schema* schema, const int32_t* path, int32_t path_len,
+                        int32_t side, fury_schema** out);
+int fury_row_explode(const fury_schema* schema, const int32_t* path, int32_t path_len, int32_t side,
+                     const void* rows, const int64_t* row_offsets, int64_t nrows,
+                     int64_t* out_list_offsets, uint8_t* out_entry_validity,
+                     int64_t elem_capacity,
+                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, int64_t* out_count,
+                     int64_t* out_parents, int32_t* out_ordinals, uint8_t* out_validity,
                      void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
