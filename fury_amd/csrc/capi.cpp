@@ -1205,6 +1205,84 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
   return launch_filter(a, row_mask, out_count, out_indices, hs);
 }
 
+// A subset of the fields, as rows (select.hip): BinaryRow's getters feeding a BinaryRowWriter of the
+// selected schema.  The host turns the selection into the int32 table SelectArgs describes.
+int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_selected,
+                    const void* rows, const int64_t* row_offsets, int64_t nrows, void* out_rows,
+                    int64_t out_capacity, int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_select");
+  int st = check_field_selection(s, fields, num_selected, f);
+  if (st) return st;
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (misaligned(row_offsets, 8) || misaligned(out_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets / out_offsets must be 8-byte aligned");
+  std::vector<int32_t> table(4 * static_cast<size_t>(num_selected));
+  std::vector<int32_t> var_fields;
+  for (int32_t j = 0; j < num_selected; j++) {
+    const int32_t k = fields[j];
+    const FieldPlan& p = s->plan[k];
+    int32_t* t = &table[4 * static_cast<size_t>(j)];
+    t[0] = k;
+    t[2] = 0;
+    t[3] = -1;
+    if (p.width > 0) {
+      t[1] = p.kind == kBool ? kSelBool : p.width;
+      continue;
+    }
+    t[1] = kSelVar;
+    t[3] = static_cast<int32_t>(var_fields.size());
+    var_fields.push_back(j);
+    switch (p.type_id) {
+      case FURY_TYPE_DECIMAL: t[2] = 16 | kSelExact; break;
+      case FURY_TYPE_STRUCT: {          // a row of the child's fields: at least its header
+        const int64_t m = static_cast<int64_t>(s->fields[k].children.size());
+        t[2] = static_cast<int32_t>(std::min<int64_t>(bitmap_bytes(m) + 8 * m, kSelNeed)) | kSelMod8;
+        break;
+      }
+      case FURY_TYPE_LIST:
+      case FURY_TYPE_MAP: t[2] = 8 | kSelMod8; break;    // [int64 numElements] / [int64 keyArrayBytes]
+      default: break;                   // STRING / BINARY: any size
+    }
+  }
+  const bool sel_fixed = var_fields.empty();
+  const int32_t out_bitmap = bitmap_bytes(num_selected);
+  const int64_t out_fixed = out_bitmap + 8 * static_cast<int64_t>(num_selected);
+  if (!s->is_fixed && !row_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
+  if (!sel_fixed && !out_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": a selection with a variable-length field needs out_offsets");
+  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  if (sel_fixed && out_rows && out_capacity / out_fixed < nrows)
+    return set_error(FURY_ERR_CAPACITY,
+                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
+                         " rows of " + std::to_string(out_fixed) + " bytes");
+  st = take_device_error(hs);
+  if (st) return st;
+  table.insert(table.end(), var_fields.begin(), var_fields.end());
+  SelectArgs a{};
+  a.rows = static_cast<const uint8_t*>(rows);
+  a.row_offsets = s->is_fixed ? nullptr : row_offsets;    // fixed schemas: row i at i * fixed_size
+  a.nrows = nrows;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  a.bitmap_bytes = s->bitmap_bytes;
+  a.fixed_size = s->fixed_size;
+  a.nsel = num_selected;
+  a.nvar = static_cast<int32_t>(var_fields.size());
+  a.out_bitmap_bytes = out_bitmap;
+  a.out_fixed_size = static_cast<int32_t>(out_fixed);
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_select(a, table.data(), static_cast<int>(table.size()), hs);
+}
+
 // Nested values as batches (extract.hip): getStruct / getArray / getMap over a batch.  The path is
 // resolved on the host (schema.cpp); the per-level widths travel in the argument block.
 int fury_row_extract(const fury_schema* s, const int32_t* path, int32_t path_len, const void* rows,

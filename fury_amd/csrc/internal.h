@@ -114,6 +114,11 @@ struct ExplodePath {
 int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
                          const std::string& f, ExplodePath* out);
 
+// The selection rules fury_schema_select and fury_row_select share (schema.cpp; rules and messages in
+// include/fury_row.h): top-level slots of a row schema, any order, no duplicates, no count limit.
+int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t num_selected,
+                          const std::string& f);
+
 inline int32_t bitmap_bytes(int64_t n) { return static_cast<int32_t>(((n + 63) / 64) * 8); }
 inline int64_t round8(int64_t n) { return (n + 7) & ~int64_t(7); }
 

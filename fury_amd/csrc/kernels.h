@@ -391,6 +391,38 @@ struct ExplodeArgs {
 };
 int launch_explode(const ExplodeArgs& a, hipStream_t stream);
 
+// ---- a subset of a row's fields, as rows: select.hip ---------------------------------------------
+// BinaryRow's getters feeding a fresh BinaryRowWriter of the selected schema, over a batch: output
+// row r holds field fields[j] of source row r in slot j.  The selection travels as a table of int32
+// words: 4 per selected field j -- [4 j] source slot, [4 j + 1] width (1 / 2 / 4 / 8 bytes, kSelBool,
+// kSelVar), [4 j + 2] the least size of a variable-length value | kSelMod8 (size % 8 == 0) |
+// kSelExact (size == least), [4 j + 3] its index among the selected variable-length fields or -1 --
+// followed by one word per variable-length field: its j.  Up to kSelArgWords words sit in the
+// argument block; a longer table is uploaded (SelectArgs.tab).  Bounds = "Decode bounds" above: a row
+// whose header leaves [0, total), starts off an 8-byte boundary or is shorter than fixed_size comes
+// out all null; a value whose slot is negative, misaligned, leaves [0, total) or misses its size rule
+// comes out null; both raise kErrBounds with the row.  out NULL: the measure form; bytes at or past
+// `cap` are never written while out_offsets is always complete.  Asynchronous on `stream`.
+constexpr int kSelArgWords = 320;     // 64 selected fields, every one variable-length
+constexpr int32_t kSelBool = 0, kSelVar = -1;
+constexpr int32_t kSelMod8 = 1 << 30, kSelExact = 1 << 29, kSelNeed = kSelExact - 1;
+struct SelectArgs {
+  int32_t tabi[kSelArgWords];
+  const int32_t* tab;                 // device table when it outgrows tabi, else NULL
+  const uint8_t* rows;
+  const int64_t* row_offsets;         // NULL: fixed-size source rows (row r at r * fixed_size)
+  int64_t nrows;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries; optional when the selection is fixed-width
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t bitmap_bytes, fixed_size;   // source rows
+  int32_t nsel, nvar;                 // selected fields, variable-length ones among them
+  int32_t out_bitmap_bytes, out_fixed_size;
+};
+// `table`: the nwords words described above (host); copied into the argument block or uploaded.
+int launch_select(const SelectArgs& a, const int32_t* table, int nwords, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

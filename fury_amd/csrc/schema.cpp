@@ -253,6 +253,32 @@ int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path
   return FURY_OK;
 }
 
+int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t nsel,
+                          const std::string& f) {
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a collection schema has no row fields to select (its entries are "
+                         "arrays / maps, not rows)");
+  if (!fields) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": fields is null");
+  if (nsel < 1 || nsel > s->num_fields)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_selected " + std::to_string(nsel) + " is not in [1, " +
+                         std::to_string(s->num_fields) + "]");
+  std::vector<char> seen(s->num_fields, 0);
+  for (int32_t j = 0; j < nsel; j++) {
+    const int32_t k = fields[j];
+    if (k < 0 || k >= s->num_fields)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": fields[" + std::to_string(j) + "] = " +
+                                                      std::to_string(k) + " is not a field of the schema");
+    if (seen[k])
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name + ") selected twice");
+    seen[k] = 1;
+  }
+  return FURY_OK;
+}
+
 // The fury_field tree of OwnedFields (names point into them); `keep` owns the child arrays.
 static void c_fields(const std::vector<OwnedField>& in, std::vector<fury_field>* out,
                      std::vector<std::vector<fury_field>>* keep) {
@@ -491,6 +517,22 @@ int fury_schema_element(const fury_schema* s, const int32_t* path, int32_t path_
   const std::vector<OwnedField> one{*p.elem};         // lives until the schema has copied it
   c_fields(one, &top, &keep);
   return fury_collection_schema_create(top.data(), out);
+}
+
+int fury_schema_select(const fury_schema* s, const int32_t* fields, int32_t num_selected,
+                       fury_schema** out) {
+  const std::string f("fury_schema_select");
+  if (!out) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out is null");
+  *out = nullptr;
+  int st = check_field_selection(s, fields, num_selected, f);
+  if (st) return st;
+  std::vector<OwnedField> chosen;
+  chosen.reserve(num_selected);
+  for (int32_t j = 0; j < num_selected; j++) chosen.push_back(s->fields[fields[j]]);
+  std::vector<fury_field> top;
+  std::vector<std::vector<fury_field>> keep;
+  c_fields(chosen, &top, &keep);
+  return fury_schema_create(top.data(), num_selected, out);
 }
 
 int32_t fury_schema_num_nodes(const fury_schema* s) {

@@ -859,6 +859,82 @@ class RowEncoder:
         out = RowBatch(rows[:total], offs, count, self.schema_hash)
         return (out, kept) if return_indices else out
 
+    # -- field selection: a subset of the fields, as rows (getters feeding a BinaryRowWriter) -----
+    def selected_encoder(self, select: Sequence) -> "RowEncoder":
+        """The ``RowEncoder`` of the fields ``select`` (names or slot indices, in selection order,
+        no duplicates), on this encoder's device and cached per selection: the codec of what
+        ``select_fields`` returns."""
+        idx = self._select(select)
+        cache = self.__dict__.setdefault("_selected", {})
+        enc = cache.get(tuple(idx))
+        if enc is None:
+            sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+            h = ctypes.c_void_p()              # the library checks the selection: its rules, its messages
+            _check(N.lib().fury_schema_select(self._schema.handle, sel, len(idx), ctypes.byref(h)))
+            N.lib().fury_schema_destroy(h)
+            enc = RowEncoder([self._schema.fields[k] for k in idx], self.device)
+            cache[tuple(idx)] = enc
+        return enc
+
+    def _select_args(self, batch: RowBatch, select: Sequence, out_rows, out_offsets, stream,
+                     keep: list):
+        self._check_hash(batch)
+        idx = self._select(select)
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        return (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets),
+                _stream_handle(stream))
+
+    def select_fields_into(self, batch: RowBatch, select: Sequence,
+                           out_rows: Optional[torch.Tensor],
+                           out_offsets: Optional[torch.Tensor] = None, stream=None) -> None:
+        """Row r of the output = the fields ``select`` (names or slot indices, any order, no
+        duplicates) of row r of ``batch``, as a row of ``selected_encoder(select)``: written to the
+        preallocated ``out_rows`` (capacity = its size) with the offsets in ``out_offsets`` (int64,
+        nrows + 1 entries; optional when every selected field is fixed-width).  One call, no host
+        synchronisation; every field type may be selected, nested ones included.  Capacity and
+        ``out_rows=None`` as in ``take_into``; a malformed value comes out null, a malformed row all
+        null, both reported by ``device_status(stream)``.  ``out_rows`` must not overlap
+        ``batch.rows``."""
+        keep: list = []
+        _check(N.lib().fury_row_select(*self._select_args(batch, select, out_rows, out_offsets,
+                                                          stream, keep)))
+
+    def bind_select_fields(self, batch: RowBatch, select: Sequence,
+                           out_rows: Optional[torch.Tensor],
+                           out_offsets: Optional[torch.Tensor] = None, stream=None):
+        """``select_fields_into`` bound like ``bind_take``: selection and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_select
+        args = self._select_args(batch, select, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def select_fields(self, batch: RowBatch, select: Sequence, stream=None) -> RowBatch:
+        """The fields ``select`` of every row of ``batch`` as a new batch of
+        ``selected_encoder(select)`` (its ``schema_hash``).  A fixed-width selection knows its size
+        up front; the others measure first (one host read of the byte total), then write."""
+        self._check_hash(batch)
+        idx = self._select(select)
+        child = self.selected_encoder(idx)
+        n = batch.nrows
+        with _on(stream):
+            if child.schema().is_fixed:
+                offs = None
+                total = n * child.schema().fixed_size
+            else:
+                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                self.select_fields_into(batch, idx, None, offs, stream)
+                total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.select_fields_into(batch, idx, rows, offs, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, child.schema_hash)
+
     # -- nested values as batches (BinaryRow.getStruct / getArray / getMap over a batch) ----------
     def _path(self, path) -> List[int]:
         """Slot indices of ``path``: field names or slot indices from the top level down through

@@ -51,6 +51,12 @@
  *                           as a batch of the element schema (fury_schema_element)
  *                           (FMT/row/binary/BinaryArray.java:137-150,
  *                            FMT/row/binary/BinaryMap.java:101-108)
+ *   fury_row_select         BinaryRow getters feeding BinaryRowWriter.write(ordinal, <primitive>) /
+ *                           BinaryWriter.writeUnaligned / write(ordinal, BinaryRow | BinaryArray |
+ *                           BinaryMap) -> writeAlignedBytes / copyTo over a batch: a subset of every
+ *                           row's fields as rows of the selected schema (fury_schema_select)
+ *                           (FMT/row/binary/writer/BinaryWriter.java:161-212,243-245,
+ *                            FMT/row/binary/writer/BinaryRowWriter.java:86-129)
  *   fury_rows_to_arrow     ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -472,6 +478,66 @@ int fury_row_explode(const fury_schema* schema, const int32_t* path, int32_t pat
                      void* out_rows, int64_t out_capacity, int64_t* out_offsets, int64_t* out_count,
                      int64_t* out_parents, int32_t* out_ordinals, uint8_t* out_validity,
                      void* stream);
+
+/* A subset of the fields, as rows -- the relational partner of take / filter (Spark's
+ * UnsafeProjection): keep, drop and reorder top-level fields without leaving row bytes.  Per row it is
+ * BinaryRow's getters feeding a fresh BinaryRowWriter of the selected schema: write(ordinal,
+ * <primitive>) for a fixed-width field (FMT/row/binary/writer/BinaryRowWriter.java:86-129),
+ * writeUnaligned / write(ordinal, BinaryRow | BinaryArray | BinaryMap) -> writeAlignedBytes / copyTo for
+ * a variable-length one (FMT/row/binary/writer/BinaryWriter.java:161-212,243-245).  A variable-length
+ * value addresses everything below it relative to its own base, so moving it is a copy of its bytes
+ * and one rewritten slot; every field type is allowed, nested ones included.
+ *
+ * Selection (both functions, same rules, each message prefixed with the function's name):
+ * fields[0 .. num_selected) are top-level slots of `schema` in any order, without duplicates,
+ * 1 <= num_selected <= num_fields -- there is no cap on the count.  A null table, a count out of
+ * range, an index out of range or a duplicate returns FURY_ERR_INVALID_ARGUMENT; a collection schema
+ * returns FURY_ERR_UNSUPPORTED.
+ *
+ * fury_schema_select: the row schema of the selected fields in selection order (names, types,
+ * nullability and children kept; info, hash and node count equal fury_schema_create of those fields).
+ * The caller destroys it.  Host only.
+ *
+ * fury_row_select: output row r holds source field fields[j] of source row r in slot j; row count and
+ * order are unchanged.  With n, bm, F the source's field count, bitmap bytes and fixed_size, n', bm', F'
+ * those of the selected schema, total = row_offsets[nrows] and B = row_offsets[r] (r * F when the source
+ * is_fixed: a non-NULL row_offsets is then ignored, as in fury_row_project), per row:
+ *   1. B must be a multiple of 8, [B, B + F) must lie in [0, total) and the row's own extent
+ *      (row_offsets[r + 1] - B) must be >= F (fury_row_update's rule); otherwise the ROW fails: its
+ *      output is F' bytes with bitmap bits [0, n') set and every slot 0, and FURY_ERR_OUT_OF_BOUNDS is
+ *      reported on `stream` (fury_device_status) naming row r;
+ *   2. source bit k = fields[j] set: output bit j is set and slot j is 0; the source slot is not read;
+ *   3. a fixed-width field of width w: slot j = bytes [0, w) of the source slot, zero-extended to 8
+ *      bytes; a BOOL byte becomes 1 when non-zero, else 0;
+ *   4. a variable-length field: off = (int32)(slot >> 32), size = (int32)slot.  The VALUE fails unless
+ *      off >= 0, size >= 0, off % 8 == 0 (every writer places values at the 8-aligned writer index),
+ *      [B + off, B + off + size) lies in [0, total), a DECIMAL has size == 16, a STRUCT / LIST / MAP has
+ *      size % 8 == 0 with size >= the child's header (bitmap + 8 per field) for a STRUCT and size >= 8 for
+ *      a LIST / MAP.  A failed value becomes null as in 2 and FURY_ERR_OUT_OF_BOUNDS names row r.  A
+ *      valid one is copied unchanged to the row's current end W (W starts at F' and advances in
+ *      selection order), the tail up to the next multiple of 8 is zeros (source padding is not copied),
+ *      slot j = (W << 32) | size, and W advances by size rounded up to 8; a size-0 value still gets its
+ *      slot.  Should W exceed INT32_MAX - 7 the row fails as in 1 (only rows whose slots alias one
+ *      large span get there);
+ *   5. the row's size is the final W, a multiple of 8.
+ * out_offsets[0 .. nrows] is the exclusive scan of the row sizes.  out_rows, out_capacity and the
+ * measure form (out_rows == NULL) behave exactly as in fury_row_take: bytes at or past the capacity are
+ * never written, out_offsets is always complete.  When the selected schema is_fixed, output row r sits
+ * at r * F', out_offsets may be NULL, and out_rows != NULL with out_capacity < nrows * F' returns
+ * FURY_ERR_CAPACITY before any device work; otherwise out_offsets is required.  row_offsets is required
+ * unless the source is_fixed.  nrows == 0 writes out_offsets[0] = 0 when given.
+ * For rows any writer made the result equals fury_row_encode of the selected columns under the selected
+ * schema byte for byte, and selecting every field in order returns the source bytes; for any input the
+ * output is canonical (zero padding, zero null slots, zero upper slot bytes).
+ * `rows` and `out_rows` are 8-byte aligned and must not overlap; nothing outside [rows, rows + total)
+ * is read and nothing outside [out_rows, out_rows + min(out_capacity, needed)) and out_offsets is
+ * written.  Asynchronous on `stream`, no host synchronisation; argument errors are returned before any
+ * device work, a pending device error of the stream first. */
+int fury_schema_select(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
+                       fury_schema** out);
+int fury_row_select(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
+                    const void* rows, const int64_t* row_offsets, int64_t nrows,
+                    void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)

@@ -1,0 +1,498 @@
+"""Field selection on the GPU (fury_row_select, RowEncoder.select_fields / select_fields_into /
+bind_select_fields): the whole output buffer, 4096 guard bytes on each side included, and the whole
+out_offsets equal the numpy model of tests/test_select_model.py (pinned there to the oracle), computed
+from the source bytes alone.  Marked gpu."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+from fury_amd import types as T  # noqa: E402
+from fury_amd.workloads import SCHEMAS  # noqa: E402
+from tests.helpers import assert_columns_equal  # noqa: E402
+from tests.test_select_abi import STRUCT100_SELECTIONS  # noqa: E402
+from tests.test_select_model import ONE, expect_select, host_columns, selections  # noqa: E402
+
+GUARD = 4096
+FILL = 0xAB
+COUNTS = [1, 63, 64, 65, 257, 4097]
+SIZES = [0, 1, 7, 8, 9, 300]
+BIG = 70000
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch.device("cuda:0")
+
+
+# -- sources: encoded once by the oracle, kept on the host, never modified ---------------------------
+def wide_fields():
+    """130 fields, INT32 / STRING alternating: three bitmap words."""
+    return [T.field(f"w{i:03d}", T.STRING if i % 2 else T.INT32) for i in range(130)]
+
+
+def sizes_fields():
+    return [T.field("id", T.INT32), T.field("s", T.STRING), T.field("t", T.BINARY)]
+
+
+def _sizes_beans(n):
+    def text(i):
+        return "q" * (BIG if i == 17 else SIZES[i % len(SIZES)])
+    return [{"id": i, "s": None if i % 13 == 5 else text(i),
+             "t": None if i % 11 == 3 else bytes((i + j) % 251 for j in range(SIZES[(i + 2) % len(SIZES)]))}
+            for i in range(n)]
+
+
+def _full_beans(n):
+    """foo with every nested field present in every row (the malformed-slot tests edit row 3)."""
+    return [{"f1": i, "f2": f"s{i}", "f3": [f"x{j}" for j in range(1 + i % 3)],
+             "f4": [(f"k{j}", j) for j in range(1 + i % 2)], "f5": {"f1": i, "f2": "b" * (1 + i % 9)}}
+            for i in range(n)]
+
+
+class _Src:
+    def __init__(self, dev, fields, host, n):
+        from fury_amd.encoder import Encoders
+        from oracle import oracle as O
+        self.dev, self.fields, self.host, self.n = dev, fields, host, n
+        self.enc = Encoders.bean(fields, device=dev)
+        rows, offs = O.encode(fields, host, n)
+        self.rows = np.asarray(rows, np.uint8).copy()
+        self.offs = np.asarray(offs, np.int64).copy()     # explicit for fixed-width schemas too
+        self.fixed = bool(self.enc.schema().is_fixed)
+        assert int(self.offs[n]) == len(self.rows)
+        self._want: dict = {}
+
+    def sel(self, select):
+        return tuple(self.enc._select(select))
+
+    def want(self, select):
+        """The expectation for the unmodified bytes, computed once per selection."""
+        key = self.sel(select)
+        if key not in self._want:
+            self._want[key] = expect_select(self.rows, self.offs, self.n, self.fields, list(key))
+        return self._want[key]
+
+
+_CACHE: dict = {}
+
+
+def source(dev, name, n) -> _Src:
+    from fury_amd.beans import beans_to_columns
+    from fury_amd.workloads import gen_columns
+    key = (name, n)
+    if key not in _CACHE:
+        if name == "wide":
+            fields = wide_fields()
+            host = gen_columns(None, fields, n, seed=9, null_pct=10, str_max=20)
+        elif name == "sizes":
+            fields = sizes_fields()
+            host = beans_to_columns(fields, _sizes_beans(n))
+        elif name == "full":
+            fields = SCHEMAS["foo"]
+            host = beans_to_columns(fields, _full_beans(n))
+        else:
+            fields = SCHEMAS[name]
+            host = host_columns(name, n)
+        _CACHE[key] = _Src(dev, fields, host, n)
+    return _CACHE[key]
+
+
+# -- one call into guarded buffers, everything compared ---------------------------------------------------
+def assert_same(got, want, what):
+    if got.shape != want.shape or not np.array_equal(got, want):
+        at = np.flatnonzero(got != want) if got.shape == want.shape else []
+        raise AssertionError(f"{what}: shapes {got.shape} / {want.shape}, {len(at)} entries differ, "
+                             f"first at {at[:8]} (got {got[at[:8]]}, want {want[at[:8]]})")
+
+
+def _upload(src, shift=0, rows=None, offs=None):
+    from fury_amd.encoder import RowBatch
+    rows = src.rows if rows is None else rows
+    t = torch.empty(len(rows) + 16, dtype=torch.uint8, device=src.dev)
+    assert t.data_ptr() % 16 == 0
+    d = t[shift:shift + len(rows)]
+    d.copy_(torch.from_numpy(rows))
+    o = None
+    if not src.fixed:
+        o = torch.from_numpy(np.asarray(src.offs if offs is None else offs, np.int64)).to(src.dev)
+    return RowBatch(d, o, src.n, src.enc.schema_hash)
+
+
+def check_select(src, select, what, cap=None, src_shift=0, out_shift=0, measure=False, stream=None,
+                 bound=False, calls=1, rows=None, offs=None, with_offsets=True):
+    dev, n = src.dev, src.n
+    sel = list(src.sel(select))
+    if rows is None and offs is None:
+        w = src.want(sel)
+    else:
+        w = expect_select(src.rows if rows is None else rows, src.offs if offs is None else offs, n,
+                          src.fields, sel)
+    cap = len(w.data) if cap is None else cap
+    batch = _upload(src, src_shift, rows, offs)
+    t = torch.full((GUARD + 16 + cap + GUARD,), FILL, dtype=torch.uint8, device=dev)
+    assert t.data_ptr() % 16 == 0
+    at = GUARD + out_shift
+    out = t[at:at + cap]
+    ooffs = torch.full((n + 2,), -7, dtype=torch.int64, device=dev)
+    args = (batch, sel, None if measure else out, ooffs[:n + 1] if with_offsets else None)
+    torch.cuda.synchronize()
+    if bound:
+        call = src.enc.bind_select_fields(*args, stream=stream)
+        for _ in range(calls):
+            call()
+    else:
+        for _ in range(calls):
+            src.enc.select_fields_into(*args, stream=stream)
+    torch.cuda.synchronize()
+    assert_same(ooffs.cpu().numpy(), np.concatenate([w.offs, [-7]]) if with_offsets
+                else np.full(n + 2, -7, np.int64), f"{what}: out_offsets")
+    want = np.full(t.numel(), FILL, np.uint8)
+    if not measure:
+        k = min(cap, len(w.data))
+        want[at:at + k] = w.data[:k]
+    assert_same(t.cpu().numpy(), want, f"{what}: output buffer")
+    return w
+
+
+# 1. every schema x selection x row count ------------------------------------------------------------------
+@pytest.mark.parametrize("n", COUNTS)
+def test_select_struct100(dev, n):
+    src = source(dev, "struct100", n)
+    for what, sel in STRUCT100_SELECTIONS.items():
+        w = check_select(src, sel, f"struct100 {what} n={n}")
+        assert not w.bad and len(w.data) == n * T.fixed_size([src.fields[k] for k in sel])
+        check_select(src, sel, f"struct100 {what} n={n} without out_offsets, 8 mod 16", out_shift=8,
+                     with_offsets=False)
+    src.enc.device_status()
+
+
+@pytest.mark.parametrize("n", COUNTS)
+@pytest.mark.parametrize("name", ["mixed", "narrow", "foo", "beana"])
+def test_select_variable(dev, name, n):
+    src = source(dev, name, n)
+    for what, sel in selections(src.fields, ONE[name]).items():
+        w = check_select(src, sel, f"{name} {what} n={n}")
+        assert not w.bad
+        if what == "all":
+            assert_same(w.data, src.rows, f"{name}: every field in order is the source")
+    src.enc.device_status()
+
+
+@pytest.mark.parametrize("n", [65, 4097])
+def test_fixed_fields_of_variable_rows(dev, n):
+    """No variable-length field selected: the no-scan kernel reading rows at row_offsets."""
+    for name, sel in (("mixed", ["c", "a"]), ("narrow", ["m_long", "a_bool", "b_byte", "c_short", "e_float"]),
+                      ("foo", ["f1"]), ("wide", list(range(128, -1, -2)))):      # 65 INT32 fields
+        src = source(dev, name, n)
+        for with_offsets in (True, False):
+            w = check_select(src, sel, f"{name} {sel} n={n} offsets={with_offsets}", out_shift=8,
+                             with_offsets=with_offsets)
+            assert not w.bad
+        assert src.enc.selected_encoder(sel).schema().is_fixed
+        src.enc.device_status()
+
+
+@pytest.mark.parametrize("n", [65, 257])
+def test_select_129_of_130_fields(dev, n):
+    src = source(dev, "wide", n)
+    assert src.enc.schema().bitmap_bytes == 24
+    for drop in (0, 64, 129):
+        sel = [k for k in range(130) if k != drop]
+        assert src.enc.selected_encoder(sel).schema().bitmap_bytes == 24
+        w = check_select(src, sel, f"wide without field {drop} n={n}")
+        assert not w.bad
+    check_select(src, list(range(129, -1, -1)), f"wide reversed n={n}", out_shift=8)
+    src.enc.device_status()
+
+
+def test_value_sizes(dev):
+    src = source(dev, "sizes", 65)
+    assert int(src.offs[18] - src.offs[17]) > BIG               # one value of 70,000 bytes in row 17
+    for sel in (["s"], ["t", "s"], ["s", "id"], ["t", "id", "s"]):
+        for out_shift in (0, 8):
+            w = check_select(src, sel, f"sizes {sel} shift {out_shift}", out_shift=out_shift)
+            assert not w.bad
+    src.enc.device_status()
+
+
+# 2. round trips -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["mixed", "narrow", "foo"])
+def test_round_trips(dev, name):
+    from fury_amd.encoder import column_to_device, column_to_host
+    n = 257
+    src = source(dev, name, n)
+    sel = selections(src.fields, ONE[name])["half"]
+    child = src.enc.selected_encoder(sel)
+    fields = [src.fields[k] for k in sel]
+    got = src.enc.select_fields(_upload(src), sel)
+    w = src.want(sel)
+    assert got.nrows == n and got.schema_hash == child.schema_hash
+    assert_same(got.rows.cpu().numpy(), w.data, f"{name}: select_fields rows")
+    assert_same(got.row_offsets.cpu().numpy(), w.offs, f"{name}: select_fields offsets")
+    # decode with the selected encoder = the column subset
+    dec = [column_to_host(c) for c in child.decode_batch(got)]
+    from oracle import oracle as O
+    ref = O.decode(fields, w.data, w.offs, n)
+    assert_columns_equal(fields, dec, ref, n)
+    full = O.decode(src.fields, src.rows, src.offs, n)
+    assert_columns_equal(fields, dec, [full[k] for k in sel], n)
+    # = encode_batch of the selected columns
+    enc = child.encode_batch([column_to_device(src.host[k], dev) for k in sel], n)
+    assert_same(got.rows.cpu().numpy(), enc.rows.cpu().numpy(), f"{name}: encode of the subset")
+    assert_same(got.row_offsets.cpu().numpy(), enc.row_offsets.cpu().numpy(), f"{name}: its offsets")
+    # select of select = the composed selection
+    inner = list(range(len(sel) - 1, -1, -2))
+    twice = child.select_fields(got, inner)
+    once = src.enc.select_fields(_upload(src), [sel[i] for i in inner])
+    assert twice.schema_hash == once.schema_hash
+    assert_same(twice.rows.cpu().numpy(), once.rows.cpu().numpy(), f"{name}: select of select")
+    if once.row_offsets is not None:
+        assert_same(twice.row_offsets.cpu().numpy(), once.row_offsets.cpu().numpy(),
+                    f"{name}: select of select offsets")
+
+
+def test_fixed_selection_returns_a_fixed_batch(dev):
+    src = source(dev, "struct100", 257)
+    sel = STRUCT100_SELECTIONS["ten spread"]
+    got = src.enc.select_fields(_upload(src), sel)
+    assert got.row_offsets is None and got.nrows == 257
+    assert_same(got.rows.cpu().numpy(), src.want(sel).data, "struct100: select_fields rows")
+    back = src.enc.selected_encoder(sel).decode_batch(got)
+    from fury_amd.encoder import column_to_host
+    from oracle import oracle as O
+    full = O.decode(src.fields, src.rows, src.offs, 257)
+    assert_columns_equal([src.fields[k] for k in sel], [column_to_host(c) for c in back],
+                         [full[k] for k in sel], 257)
+
+
+# 3. canonical output for non-canonical input ----------------------------------------------------------------
+def _slot_pos(src, r, name):
+    k = [f.name for f in src.fields].index(name)
+    return int(src.offs[r]) + src.enc.schema().bitmap_bytes + 8 * k, k
+
+
+def _is_null(src, r, k):
+    return bool((src.rows[int(src.offs[r]) + (k >> 3)] >> (k & 7)) & 1)
+
+
+def _row_where(src, name, null, ok=lambda pos: True):
+    for r in range(src.n):
+        pos, k = _slot_pos(src, r, name)
+        if _is_null(src, r, k) == null and ok(pos):
+            return r, pos
+    raise AssertionError(f"no row with {name} null={null}")
+
+
+def _get(rows, pos):
+    s = int.from_bytes(rows[pos:pos + 8].tobytes(), "little")
+    off, size = (s >> 32) & 0xFFFFFFFF, s & 0xFFFFFFFF
+    return off - (1 << 32) * (off >> 31), size - (1 << 32) * (size >> 31)
+
+
+def _put(rows, pos, off, size):
+    rows[pos:pos + 8] = np.frombuffer(
+        (((off & 0xFFFFFFFF) << 32) | (size & 0xFFFFFFFF)).to_bytes(8, "little"), np.uint8)
+
+
+def test_canonicalisation(dev):
+    src = source(dev, "narrow", 65)
+    rows = src.rows.copy()
+    r, pos = _row_where(src, "d_int", True)
+    rows[pos:pos + 8] = 0x5A                                   # a stale slot under a null bit
+    r, pos = _row_where(src, "d_int", False)
+    rows[pos + 4:pos + 8] = 0xC3                               # upper bytes of an INT32 slot
+    r, pos = _row_where(src, "c_short", False)
+    rows[pos + 2:pos + 8] = 0x77                               # and of an INT16 slot
+    r, pos = _row_where(src, "a_bool", False)
+    rows[pos] = 2                                              # a BOOL byte of 2
+    r, pos = _row_where(src, "i_bin", False, lambda p: _get(src.rows, p)[1] % 8 not in (0, 7))
+    off, size = _get(rows, pos)
+    at = int(src.offs[r]) + off + size
+    assert not rows[at:at + 2].any()
+    rows[at:at + 2] = 0xEE                                     # non-zero padding after a value
+    full = list(range(len(src.fields)))
+    for sel in (full, ["i_bin", "a_bool", "d_int", "c_short"]):
+        w = check_select(src, sel, f"canonicalisation {sel}", rows=rows)
+        assert not w.bad
+        clean = src.want(sel)
+        diff = np.flatnonzero(w.data != clean.data)            # only the BOOL changed: 2 -> 1
+        assert len(diff) <= 1 and np.array_equal(w.offs, clean.offs)
+        assert all(w.data[i] == 1 for i in diff)
+    src.enc.device_status()
+
+
+# 4. malformed rows: one edit, row 3 of 65 ---------------------------------------------------------------------
+def _check_malformed(src, select, what, rows=None, offs=None, victim=3):
+    from fury_amd.encoder import IndexOutOfBoundsException
+    src.enc.device_status()
+    w = check_select(src, select, what, rows=rows, offs=offs, out_shift=8)
+    assert w.bad == [victim], what
+    with pytest.raises(IndexOutOfBoundsException, match=f"row {victim} "):
+        src.enc.device_status()
+    src.enc.device_status()                               # raised once, then clear
+    return w
+
+
+VALUE_EDITS = {
+    "size -1": ("f2", lambda off, size, total: (off, -1)),
+    "off past the batch": ("f2", lambda off, size, total: (total + 64, size)),
+    "off % 8 == 4": ("f2", lambda off, size, total: (off + 4, size)),
+    "struct size % 8 != 0": ("f5", lambda off, size, total: (off, size - 4)),
+    "struct size below its header": ("f5", lambda off, size, total: (off, 16)),
+    "list size below 8": ("f3", lambda off, size, total: (off, 0)),
+}
+
+
+@pytest.mark.parametrize("edit", list(VALUE_EDITS))
+def test_malformed_value_becomes_null(dev, edit):
+    src = source(dev, "full", 65)
+    name, fn = VALUE_EDITS[edit]
+    rows = src.rows.copy()
+    pos, k = _slot_pos(src, 3, name)
+    assert not _is_null(src, 3, k)
+    _put(rows, pos, *fn(*_get(rows, pos), len(rows)))
+    for sel in (["f5", "f3", "f2", "f1"], [name]):
+        w = _check_malformed(src, sel, f"{edit}: {sel}", rows=rows)
+        j = sel.index(name)
+        head = w.data[int(w.offs[3]):int(w.offs[4])]
+        assert (head[0] >> j) & 1 and not head[8 + 8 * j:16 + 8 * j].any()     # null, slot 0
+    check_select(src, ["f5", "f3", "f2", "f1"], f"{edit}: the next call is clean")
+    src.enc.device_status()
+
+
+def test_decimal_of_another_size(dev):
+    src = source(dev, "beana", 65)
+    rows = src.rows.copy()
+    pos, k = _slot_pos(src, 3, "f16")
+    assert not _is_null(src, 3, k)
+    off, size = _get(rows, pos)
+    assert size == 16
+    _put(rows, pos, off, 8)
+    _check_malformed(src, ["f17", "f16", "f1"], "decimal of 8 bytes", rows=rows)
+    _check_malformed(src, list(range(len(src.fields))), "decimal of 8 bytes, every field", rows=rows)
+
+
+def test_malformed_row_becomes_all_null(dev):
+    src = source(dev, "full", 65)
+    sel = ["f5", "f2", "f1"]
+    F2 = T.fixed_size([src.fields[4], src.fields[1], src.fields[0]])
+    offs = src.offs.copy()
+    offs[3] += 1                                              # an odd row start
+    w = _check_malformed(src, sel, "odd row offset", offs=offs)
+    assert int(w.offs[4] - w.offs[3]) == F2 and w.data[int(w.offs[3])] == 7
+    w = _check_malformed(src, ["f1"], "odd row offset, fixed-width selection", offs=offs)
+    assert w.data[3 * 16:4 * 16].tolist() == [1] + [0] * 15
+    wide = source(dev, "wide", 65)                            # 65 fixed-width fields: bitmap words by ballot
+    offs = wide.offs.copy()
+    offs[3] += 1
+    w = _check_malformed(wide, list(range(0, 130, 2)), "odd row offset, 65 INT32 fields", offs=offs)
+    assert w.data[3 * 536:3 * 536 + 16].tolist() == [255] * 8 + [1] + [0] * 7
+    # the last row's extent shorter than its header: the batch ends 8 bytes into its slots
+    F = src.enc.schema().fixed_size
+    offs = src.offs.copy()
+    offs[65] = offs[64] + F - 8
+    rows = src.rows[:int(offs[65])].copy()
+    for s in (sel, ["f1"]):
+        w = _check_malformed(src, s, f"truncated last row {s}", rows=rows, offs=offs, victim=64)
+    # ... and a row whose own extent is shorter than the header while the batch goes on
+    offs = src.offs.copy()
+    offs[4] = offs[3] + F - 8
+    w = check_select(src, sel, "row 3 shorter than its header", offs=offs)
+    assert 3 in w.bad
+    with pytest.raises(IndexError):
+        src.enc.device_status()
+    src.enc.device_status()
+
+
+def test_a_corrupt_unselected_slot_is_no_error(dev):
+    src = source(dev, "full", 65)
+    rows = src.rows.copy()
+    for name in ("f3", "f4"):
+        pos, _ = _slot_pos(src, 3, name)
+        _put(rows, pos, len(rows) + 64, -8)
+    src.enc.device_status()
+    for sel in (["f5", "f2", "f1"], ["f1"]):
+        w = check_select(src, sel, f"corrupt f3 / f4 slots, {sel} selected", rows=rows)
+        assert not w.bad and np.array_equal(w.data, src.want(sel).data)
+    src.enc.device_status()
+
+
+# 5. capacity, alignment, streams ----------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["mixed", "foo"])
+def test_select_capacity(dev, name):
+    src = source(dev, name, 257)
+    sel = selections(src.fields, ONE[name])["half"]
+    total = len(src.want(sel).data)
+    assert total > 2048
+    for cap in (0, 8, total - 8, total):
+        for out_shift in (0, 8):
+            check_select(src, sel, f"{name} capacity {cap} of {total}", cap=cap, out_shift=out_shift)
+    check_select(src, sel, f"{name} measure form", measure=True)
+    src.enc.device_status()
+
+
+def test_fixed_selection_capacity(dev):
+    from fury_amd.encoder import CapacityError
+    src = source(dev, "struct100", 257)
+    sel = STRUCT100_SELECTIONS["ten spread"]
+    check_select(src, sel, "struct100 measure form", measure=True)
+    check_select(src, sel, "struct100 spare capacity", cap=257 * 88 + 24)
+    with pytest.raises(CapacityError, match="rows of 88 bytes"):
+        check_select(src, sel, "struct100 short capacity", cap=257 * 88 - 8)
+    src.enc.device_status()
+
+
+@pytest.mark.parametrize("n", [65, 4097])
+def test_select_alignment(dev, n):
+    for name, sel in (("struct100", STRUCT100_SELECTIONS["65"]), ("mixed", ["s3", "a", "s1"]),
+                      ("foo", ["f5", "f3", "f1"])):
+        src = source(dev, name, n)
+        for src_shift, out_shift in ((0, 0), (8, 0), (0, 8), (8, 8)):
+            check_select(src, sel, f"{name} n={n} shifts {src_shift}/{out_shift}",
+                         src_shift=src_shift, out_shift=out_shift)
+        src.enc.device_status()
+
+
+def test_select_on_a_side_stream_and_bound_twice(dev):
+    s = torch.cuda.Stream(device=dev)
+    for name, sel in (("struct100", STRUCT100_SELECTIONS["ten spread"]), ("foo", ["f5", "f3", "f1"])):
+        src = source(dev, name, 4097)
+        check_select(src, sel, f"{name}: select_fields_into on a side stream", stream=s, out_shift=8)
+        check_select(src, sel, f"{name}: bind_select_fields called twice", bound=True, calls=2)
+        check_select(src, sel, f"{name}: bound twice on a side stream", bound=True, calls=2, stream=s)
+        src.enc.device_status(s)
+        src.enc.device_status()
+
+
+# 6. the empty batch, and a foreign batch ------------------------------------------------------------------------
+def test_select_of_no_rows(dev):
+    from fury_amd.encoder import Encoders, RowBatch
+    enc = Encoders.bean(SCHEMAS["foo"], device=dev)
+    empty = RowBatch(torch.zeros(16, dtype=torch.uint8, device=dev)[:0],
+                     torch.zeros(1, dtype=torch.int64, device=dev), 0, enc.schema_hash)
+    out = torch.full((64,), FILL, dtype=torch.uint8, device=dev)
+    for sel in (["f5", "f1"], ["f1"]):
+        ooffs = torch.full((2,), -7, dtype=torch.int64, device=dev)
+        enc.select_fields_into(empty, sel, out, ooffs[:1])
+        torch.cuda.synchronize()
+        assert ooffs.tolist() == [0, -7] and bool((out == FILL).all())
+    enc.select_fields_into(empty, ["f1"], out, None)
+    got = enc.select_fields(empty, ["f5", "f1"])
+    assert got.nrows == 0 and got.rows.numel() == 0 and got.row_offsets.tolist() == [0]
+    assert got.schema_hash == enc.selected_encoder(["f5", "f1"]).schema_hash
+    enc.device_status()
+
+
+def test_foreign_schema_hash(dev):
+    from fury_amd.encoder import ClassNotCompatibleException, RowBatch
+    src = source(dev, "foo", 65)
+    b = _upload(src)
+    foreign = RowBatch(b.rows, b.row_offsets, b.nrows, b.schema_hash + 1)
+    with pytest.raises(ClassNotCompatibleException, match="Schema is not consistent"):
+        src.enc.select_fields(foreign, ["f5"])
