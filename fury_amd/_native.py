@@ -42,6 +42,13 @@ class FurySchemaInfo(ctypes.Structure):
                 ("schema_hash", ctypes.c_int64)]
 
 
+class FuryZipSource(ctypes.Structure):
+    _fields_ = [("schema", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+                ("row_offsets", ctypes.c_void_p)]
+
+
+ZIP_MAX_SOURCES = 4
+
 # Exported symbols with their signatures (kept in sync with include/fury_row.h; the CPU test
 # suite checks the header and this table agree).
 _P = ctypes.c_void_p
@@ -85,6 +92,10 @@ SIGNATURES = {
     "fury_schema_select": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_select": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                        _P]),
+    "fury_schema_zip": (ctypes.c_int, [ctypes.POINTER(_P), _I32, ctypes.POINTER(_I32), _I32,
+                                       ctypes.POINTER(_P)]),
+    "fury_row_zip": (ctypes.c_int, [ctypes.POINTER(FuryZipSource), _I32, ctypes.POINTER(_I32), _I32,
+                                    _I64, _P, _I64, _P, _P]),
     "fury_schema_num_nodes": (_I32, [_P]),
     "fury_decode_prepare": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(_I64),
                                            ctypes.POINTER(_I64), ctypes.POINTER(_P), _P]),

@@ -1205,6 +1205,31 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
   return launch_filter(a, row_mask, out_count, out_indices, hs);
 }
 
+// Words [0, 3) of a selected field's table entry (SelectArgs in kernels.h): the slot, the width and the
+// size rule of top-level field k of `s`; whether the field is variable-length.
+static bool selection_words(const fury_schema* s, int32_t k, int32_t* t) {
+  const FieldPlan& p = s->plan[k];
+  t[0] = k;
+  t[2] = 0;
+  if (p.width > 0) {
+    t[1] = p.kind == kBool ? kSelBool : p.width;
+    return false;
+  }
+  t[1] = kSelVar;
+  switch (p.type_id) {
+    case FURY_TYPE_DECIMAL: t[2] = 16 | kSelExact; break;
+    case FURY_TYPE_STRUCT: {            // a row of the child's fields: at least its header
+      const int64_t m = static_cast<int64_t>(s->fields[k].children.size());
+      t[2] = static_cast<int32_t>(std::min<int64_t>(bitmap_bytes(m) + 8 * m, kSelNeed)) | kSelMod8;
+      break;
+    }
+    case FURY_TYPE_LIST:
+    case FURY_TYPE_MAP: t[2] = 8 | kSelMod8; break;      // [int64 numElements] / [int64 keyArrayBytes]
+    default: break;                     // STRING / BINARY: any size
+  }
+  return true;
+}
+
 // A subset of the fields, as rows (select.hip): BinaryRow's getters feeding a BinaryRowWriter of the
 // selected schema.  The host turns the selection into the int32 table SelectArgs describes.
 int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_selected,
@@ -1224,30 +1249,11 @@ int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_sel
   std::vector<int32_t> table(4 * static_cast<size_t>(num_selected));
   std::vector<int32_t> var_fields;
   for (int32_t j = 0; j < num_selected; j++) {
-    const int32_t k = fields[j];
-    const FieldPlan& p = s->plan[k];
     int32_t* t = &table[4 * static_cast<size_t>(j)];
-    t[0] = k;
-    t[2] = 0;
     t[3] = -1;
-    if (p.width > 0) {
-      t[1] = p.kind == kBool ? kSelBool : p.width;
-      continue;
-    }
-    t[1] = kSelVar;
+    if (!selection_words(s, fields[j], t)) continue;
     t[3] = static_cast<int32_t>(var_fields.size());
     var_fields.push_back(j);
-    switch (p.type_id) {
-      case FURY_TYPE_DECIMAL: t[2] = 16 | kSelExact; break;
-      case FURY_TYPE_STRUCT: {          // a row of the child's fields: at least its header
-        const int64_t m = static_cast<int64_t>(s->fields[k].children.size());
-        t[2] = static_cast<int32_t>(std::min<int64_t>(bitmap_bytes(m) + 8 * m, kSelNeed)) | kSelMod8;
-        break;
-      }
-      case FURY_TYPE_LIST:
-      case FURY_TYPE_MAP: t[2] = 8 | kSelMod8; break;    // [int64 numElements] / [int64 keyArrayBytes]
-      default: break;                   // STRING / BINARY: any size
-    }
   }
   const bool sel_fixed = var_fields.empty();
   const int32_t out_bitmap = bitmap_bytes(num_selected);
@@ -1281,6 +1287,86 @@ int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_sel
   st = device_error_word(hs, &a.err);
   if (st) return st;
   return launch_select(a, table.data(), static_cast<int>(table.size()), hs);
+}
+
+// The fields of several batches joined row by row (zip.hip): fury_row_select with a source per pick.
+int fury_row_zip(const fury_zip_source* sources, int32_t num_sources, const int32_t* picks,
+                 int32_t num_picks, int64_t nrows, void* out_rows, int64_t out_capacity,
+                 int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_zip");
+  if (!sources) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the source table is null");
+  const fury_schema* schemas[FURY_ZIP_MAX_SOURCES] = {};
+  for (int32_t s = 0; s < num_sources && s < FURY_ZIP_MAX_SOURCES; s++) schemas[s] = sources[s].schema;
+  int st = check_zip_picks(schemas, num_sources, picks, num_picks, f);
+  if (st) return st;
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (misaligned(out_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets must be 8-byte aligned");
+  std::vector<int32_t> table(5 * static_cast<size_t>(num_picks));
+  std::vector<int32_t> var_picks;
+  uint32_t used = 0;
+  for (int32_t j = 0; j < num_picks; j++) {
+    const int32_t s = picks[2 * j];
+    int32_t* t = &table[5 * static_cast<size_t>(j)];
+    t[3] = -1;
+    t[4] = s;
+    used |= 1u << s;
+    if (!selection_words(schemas[s], picks[2 * j + 1], t)) continue;
+    t[3] = static_cast<int32_t>(var_picks.size());
+    var_picks.push_back(j);
+  }
+  for (int32_t s = 0; s < num_sources; s++) {       // a source no pick names is never read
+    if (!((used >> s) & 1)) continue;
+    const std::string src = f + ": source " + std::to_string(s);
+    if (misaligned(sources[s].rows, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows must be 8-byte aligned");
+    if (misaligned(sources[s].row_offsets, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": row_offsets must be 8-byte aligned");
+    if (!schemas[s]->is_fixed && !sources[s].row_offsets)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": variable-length rows need row_offsets");
+    if (nrows > 0 && !sources[s].rows)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows is null");
+  }
+  const bool zip_fixed = var_picks.empty();
+  const int32_t out_bitmap = bitmap_bytes(num_picks);
+  const int64_t out_fixed = out_bitmap + 8 * static_cast<int64_t>(num_picks);
+  if (out_fixed > INT32_MAX - 7)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the zipped row header exceeds 2 GiB");
+  if (!zip_fixed && !out_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": picks with a variable-length field need out_offsets");
+  if (zip_fixed && out_rows && out_capacity / out_fixed < nrows)
+    return set_error(FURY_ERR_CAPACITY,
+                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
+                         " rows of " + std::to_string(out_fixed) + " bytes");
+  st = take_device_error(hs);
+  if (st) return st;
+  table.insert(table.end(), var_picks.begin(), var_picks.end());
+  ZipArgs a{};
+  for (int32_t s = 0; s < num_sources; s++) {
+    if (!((used >> s) & 1)) continue;
+    a.src[s].rows = static_cast<const uint8_t*>(sources[s].rows);
+    // fixed schemas: row i at i * fixed_size
+    a.src[s].row_offsets = schemas[s]->is_fixed ? nullptr : sources[s].row_offsets;
+    a.src[s].bitmap_bytes = schemas[s]->bitmap_bytes;
+    a.src[s].fixed_size = schemas[s]->fixed_size;
+  }
+  a.nrows = nrows;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  a.nsel = num_picks;
+  a.nvar = static_cast<int32_t>(var_picks.size());
+  a.out_bitmap_bytes = out_bitmap;
+  a.out_fixed_size = static_cast<int32_t>(out_fixed);
+  a.used = used;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_zip(a, table.data(), static_cast<int>(table.size()), hs);
 }
 
 // Nested values as batches (extract.hip): getStruct / getArray / getMap over a batch.  The path is

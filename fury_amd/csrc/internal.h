@@ -119,6 +119,12 @@ int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path
 int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t num_selected,
                           const std::string& f);
 
+// The pick rules fury_schema_zip and fury_row_zip share (schema.cpp; rules and messages in
+// include/fury_row.h): 1 .. FURY_ZIP_MAX_SOURCES row schemas, picks = (source, top-level slot) pairs,
+// any order, no duplicate pair, no count limit.
+int check_zip_picks(const fury_schema* const* schemas, int32_t num_sources, const int32_t* picks,
+                    int32_t num_picks, const std::string& f);
+
 inline int32_t bitmap_bytes(int64_t n) { return static_cast<int32_t>(((n + 63) / 64) * 8); }
 inline int64_t round8(int64_t n) { return (n + 7) & ~int64_t(7); }
 

@@ -423,6 +423,40 @@ struct SelectArgs {
 // `table`: the nwords words described above (host); copied into the argument block or uploaded.
 int launch_select(const SelectArgs& a, const int32_t* table, int nwords, hipStream_t stream);
 
+// ---- the fields of several row batches joined row by row: zip.hip ---------------------------------
+// fury_row_select from several sources: output row r holds, in slot j, field picks[j] of row r of its
+// source.  The table has 5 int32 words per pick j -- [5 j .. 5 j + 3] as in the selection table above,
+// [5 j + 4] the source index -- followed by one word per variable-length pick: its j.  Up to
+// kZipArgWords words sit in the argument block; a longer table is uploaded (ZipArgs.tab).  Bounds =
+// "Decode bounds" above, per source s with its own total_s: a row of s that fails the row check nulls
+// the picks of s alone, a failed value comes out null, both raise kErrBounds with the row; nothing
+// outside [0, total_s) of source s is read and a source outside `used` is never read.  out, cap and
+// out_offsets as in SelectArgs.  Asynchronous on `stream`.
+constexpr int kZipMaxSources = 4;     // FURY_ZIP_MAX_SOURCES
+constexpr int kZipArgWords = 384;     // 64 picks, every one variable-length
+struct ZipSource {
+  const uint8_t* rows;
+  const int64_t* row_offsets;         // NULL: fixed-size rows (row r at r * fixed_size)
+  int32_t bitmap_bytes, fixed_size;
+};
+struct ZipArgs {
+  int32_t tabi[kZipArgWords];
+  const int32_t* tab;                 // device table when it outgrows tabi, else NULL
+  ZipSource src[kZipMaxSources];
+  int64_t nrows;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries; optional when every pick is fixed-width
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t nsel, nvar;                 // picks, variable-length ones among them
+  int32_t out_bitmap_bytes, out_fixed_size;
+  uint32_t used;                      // bit s: some pick names source s
+  int32_t pad_;
+};
+static_assert(sizeof(ZipArgs) <= 4096, "ZipArgs must fit the kernel argument block");
+// `table`: the nwords words described above (host); copied into the argument block or uploaded.
+int launch_zip(const ZipArgs& a, const int32_t* table, int nwords, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

@@ -279,6 +279,44 @@ int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t n
   return FURY_OK;
 }
 
+int check_zip_picks(const fury_schema* const* schemas, int32_t num_sources, const int32_t* picks,
+                    int32_t num_picks, const std::string& f) {
+  if (!schemas) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the source table is null");
+  if (num_sources < 1 || num_sources > FURY_ZIP_MAX_SOURCES)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_sources " + std::to_string(num_sources) + " is not in [1, " +
+                         std::to_string(FURY_ZIP_MAX_SOURCES) + "]");
+  for (int32_t s = 0; s < num_sources; s++) {
+    if (!schemas[s])
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": the schema of source " + std::to_string(s) + " is null");
+    if (schemas[s]->root != 0)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": source " + std::to_string(s) + " has a collection schema, which has no "
+                           "row fields to pick (its entries are arrays / maps, not rows)");
+  }
+  if (!picks) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": picks is null");
+  if (num_picks < 1)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_picks " + std::to_string(num_picks) + " is not >= 1");
+  std::vector<std::vector<char>> seen(num_sources);
+  for (int32_t j = 0; j < num_picks; j++) {
+    const int32_t s = picks[2 * j], k = picks[2 * j + 1];
+    const std::string at = f + ": picks[" + std::to_string(j) + "] = (" + std::to_string(s) + ", " +
+                           std::to_string(k) + ")";
+    if (s < 0 || s >= num_sources)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, at + " names no source");
+    if (k < 0 || k >= schemas[s]->num_fields)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, at + " is not a field of its source");
+    if (seen[s].empty()) seen[s].assign(schemas[s]->num_fields, 0);
+    if (seen[s][k])
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       at + " (" + schemas[s]->fields[k].name + ") picked twice");
+    seen[s][k] = 1;
+  }
+  return FURY_OK;
+}
+
 // The fury_field tree of OwnedFields (names point into them); `keep` owns the child arrays.
 static void c_fields(const std::vector<OwnedField>& in, std::vector<fury_field>* out,
                      std::vector<std::vector<fury_field>>* keep) {
@@ -533,6 +571,23 @@ int fury_schema_select(const fury_schema* s, const int32_t* fields, int32_t num_
   std::vector<std::vector<fury_field>> keep;
   c_fields(chosen, &top, &keep);
   return fury_schema_create(top.data(), num_selected, out);
+}
+
+int fury_schema_zip(const fury_schema* const* schemas, int32_t num_sources, const int32_t* picks,
+                    int32_t num_picks, fury_schema** out) {
+  const std::string f("fury_schema_zip");
+  if (!out) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out is null");
+  *out = nullptr;
+  int st = check_zip_picks(schemas, num_sources, picks, num_picks, f);
+  if (st) return st;
+  std::vector<OwnedField> chosen;
+  chosen.reserve(num_picks);
+  for (int32_t j = 0; j < num_picks; j++)
+    chosen.push_back(schemas[picks[2 * j]]->fields[picks[2 * j + 1]]);
+  std::vector<fury_field> top;
+  std::vector<std::vector<fury_field>> keep;
+  c_fields(chosen, &top, &keep);
+  return fury_schema_create(top.data(), num_picks, out);
 }
 
 int32_t fury_schema_num_nodes(const fury_schema* s) {

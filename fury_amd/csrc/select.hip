@@ -35,7 +35,7 @@
 // The selection table sits in LDS for the per-lane lookups when it has at most kSelLdsWords words.
 // Bounds (SelectArgs in kernels.h): nothing outside [0, total) of the rows buffer is read, the output
 // is written only inside [0, min(capacity, needed)).
-#include "take_dev.h"
+#include "select_dev.h"
 
 namespace fury {
 
@@ -68,23 +68,6 @@ __device__ __forceinline__ SelTable stage_table(const SelectArgs& a, int32_t* ld
     t.lds = lds;
   }
   return t;
-}
-
-__device__ __forceinline__ uint64_t word(const uint8_t* p) {
-  return *gl(reinterpret_cast<const uint64_t*>(p));
-}
-
-// A fixed-width slot as write(ordinal, <primitive>) leaves it: putInt64(offset, 0), then the value's
-// own bytes; putBoolean stores 1 or 0.
-__device__ __forceinline__ uint64_t fixed_slot(uint64_t s, int32_t width) {
-  if (width == kSelBool) return (s & 0xff) ? 1 : 0;
-  return width >= 8 ? s : s & ((1ull << (8 * width)) - 1);
-}
-
-// Bitmap word q of a row whose n fields are all null.
-__device__ __forceinline__ uint64_t all_null(int q, int n) {
-  const int left = n - 64 * q;
-  return left >= 64 ? ~0ull : (1ull << left) - 1;
 }
 
 // Source row r: its start, and whether its header may be read ("Decode bounds": 8-byte aligned,

@@ -20,7 +20,7 @@ import contextlib
 import ctypes
 import struct
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -934,6 +934,151 @@ class RowEncoder:
         self.select_fields_into(batch, idx, rows, offs, stream)
         self.device_status(stream)
         return RowBatch(rows[:total], offs, n, child.schema_hash)
+
+    # -- zip: the fields of several batches joined row by row (several BinaryRows' getters feeding
+    # one BinaryRowWriter).  ``self`` is source 0, ``others`` the (encoder, batch) pairs of sources
+    # 1 ...; ``picks`` is a sequence of (source index, field name or slot).
+    @staticmethod
+    def _picks(encoders: Sequence["RowEncoder"], picks: Sequence) -> List[Tuple[int, int]]:
+        out = []
+        for p in picks:
+            s, x = p
+            s = int(s)
+            if isinstance(x, str):
+                if not 0 <= s < len(encoders):
+                    raise IllegalArgumentException(
+                        f"pick {p!r} names source {s} of {len(encoders)} sources")
+                x = encoders[s]._select([x])[0]
+            out.append((s, int(x)))
+        return out
+
+    @staticmethod
+    def _c_picks(picks: Sequence[Tuple[int, int]]):
+        flat = [w for p in picks for w in p]
+        return (ctypes.c_int32 * max(len(flat), 2))(*flat)
+
+    def zipped_encoder(self, others_encoders: Sequence["RowEncoder"], picks: Sequence,
+                       names: Optional[Sequence[str]] = None) -> "RowEncoder":
+        """The ``RowEncoder`` of the fields ``picks`` of the sources ``[self, *others_encoders]``, in
+        pick order, on this encoder's device and cached per picks: the codec of what ``zip_fields``
+        returns.  ``names`` renames the output fields (names do not enter row bytes or the schema's
+        layout; the rename only lets callers avoid clashing names)."""
+        encoders = [self, *others_encoders]
+        idx = self._picks(encoders, picks)
+        key = (tuple(id(e) for e in others_encoders), tuple(idx), None if names is None else tuple(names))
+        cache = self.__dict__.setdefault("_zipped", {})
+        hit = cache.get(key)
+        if hit is None:
+            hs = (ctypes.c_void_p * len(encoders))(*[e._schema.handle for e in encoders])
+            h = ctypes.c_void_p()              # the library checks the picks: its rules, its messages
+            _check(N.lib().fury_schema_zip(hs, len(encoders), self._c_picks(idx), len(idx),
+                                           ctypes.byref(h)))
+            N.lib().fury_schema_destroy(h)
+            fields = [encoders[s]._schema.fields[k] for s, k in idx]
+            if names is not None:
+                if len(names) != len(fields):
+                    raise IllegalArgumentException(f"{len(names)} names for {len(fields)} picks")
+                fields = [Field(n, f.type_id, f.nullable, f.children) for n, f in zip(names, fields)]
+            hit = (RowEncoder(fields, self.device), tuple(others_encoders))   # the ids stay taken
+            cache[key] = hit
+        return hit[0]
+
+    def _zip_sources(self, batch: RowBatch, others: Sequence):
+        """The encoders and batches of all sources, schema hashes and row counts checked."""
+        encoders = [self] + [e for e, _ in others]
+        batches = [batch] + [b for _, b in others]
+        for e, b in zip(encoders, batches):
+            e._check_hash(b)
+        for s, b in enumerate(batches):
+            if b.nrows != batch.nrows:
+                raise IllegalArgumentException(
+                    f"source {s} has {b.nrows} rows, source 0 has {batch.nrows}: zip joins rows one "
+                    "to one")
+        return encoders, batches
+
+    def _zip_args(self, batch: RowBatch, others: Sequence, picks: Sequence, out_rows, out_offsets,
+                  stream, keep: list):
+        encoders, batches = self._zip_sources(batch, others)
+        n = batch.nrows
+        idx = self._picks(encoders, picks)
+        srcs = (N.FuryZipSource * max(len(encoders), 1))()
+        for s, (e, b) in enumerate(zip(encoders, batches)):
+            srcs[s].schema = e._schema.handle
+            srcs[s].rows = _ptr(b.rows)
+            srcs[s].row_offsets = _ptr(b.row_offsets)
+        cp = self._c_picks(idx)
+        keep.extend((srcs, cp, encoders, batches))
+        return (srcs, len(encoders), cp, len(idx), n, _ptr(out_rows), _nbytes(out_rows),
+                _ptr(out_offsets), _stream_handle(stream))
+
+    def zip_fields_into(self, batch: RowBatch, others: Sequence, picks: Sequence,
+                        out_rows: Optional[torch.Tensor],
+                        out_offsets: Optional[torch.Tensor] = None, stream=None) -> None:
+        """Row r of the output holds, in slot j, field ``picks[j]`` = (source, name or slot) of row r of
+        that source -- source 0 is ``batch`` (of this encoder), sources 1 ... are the ``(encoder,
+        batch)`` pairs ``others`` -- as a row of ``zipped_encoder``: written to the preallocated
+        ``out_rows`` with the offsets in ``out_offsets`` (int64, nrows + 1 entries; optional when
+        every picked field is fixed-width).  One call, no host synchronisation; every field type may
+        be picked.  Capacity, ``out_rows=None`` and malformed input as in ``select_fields_into``,
+        except that a malformed row nulls only the fields picked from its own source.  ``out_rows``
+        must not overlap any source; sources may alias each other."""
+        keep: list = []
+        _check(N.lib().fury_row_zip(*self._zip_args(batch, others, picks, out_rows, out_offsets,
+                                                    stream, keep)))
+
+    def bind_zip_fields(self, batch: RowBatch, others: Sequence, picks: Sequence,
+                        out_rows: Optional[torch.Tensor],
+                        out_offsets: Optional[torch.Tensor] = None, stream=None):
+        """``zip_fields_into`` bound like ``bind_take``: picks and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_zip
+        args = self._zip_args(batch, others, picks, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def zip_fields(self, batch: RowBatch, others: Sequence, picks: Sequence,
+                   stream=None) -> RowBatch:
+        """The fields ``picks`` of ``batch`` and of the batches in ``others``, joined row by row, as
+        a new batch of ``zipped_encoder`` (its ``schema_hash``).  Fixed-width picks know their size
+        up front; the others measure first (one host read of the byte total), then write."""
+        encoders, _ = self._zip_sources(batch, others)
+        idx = self._picks(encoders, picks)
+        child = self.zipped_encoder(encoders[1:], idx)
+        n = batch.nrows
+        with _on(stream):
+            if child.schema().is_fixed:
+                offs = None
+                total = n * child.schema().fixed_size
+            else:
+                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                self.zip_fields_into(batch, others, idx, None, offs, stream)
+                total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.zip_fields_into(batch, others, idx, rows, offs, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, child.schema_hash)
+
+    def _with_fields_picks(self, other_encoder: "RowEncoder") -> List[Tuple[int, int]]:
+        """The picks of ``with_fields``: every field of this encoder in order, a field of
+        ``other_encoder`` of the same name in its place, then the rest of ``other_encoder``."""
+        theirs = {f.name: k for k, f in enumerate(other_encoder._schema.fields)}
+        picks = [(1, theirs[f.name]) if f.name in theirs else (0, k)
+                 for k, f in enumerate(self._schema.fields)]
+        mine = {f.name for f in self._schema.fields}
+        picks += [(1, k) for k, f in enumerate(other_encoder._schema.fields) if f.name not in mine]
+        return picks
+
+    def with_fields(self, batch: RowBatch, other_encoder: "RowEncoder", other_batch: RowBatch,
+                    stream=None):
+        """Replace or append: ``batch`` with the fields of ``other_batch`` (row r to row r) -- a
+        field of ``other_encoder`` whose name this encoder has takes that field's position, whatever
+        its type, the others are appended.  Returns ``(encoder, batch)`` of the result."""
+        picks = self._with_fields_picks(other_encoder)
+        enc = self.zipped_encoder([other_encoder], picks)
+        return enc, self.zip_fields(batch, [(other_encoder, other_batch)], picks, stream)
 
     # -- nested values as batches (BinaryRow.getStruct / getArray / getMap over a batch) ----------
     def _path(self, path) -> List[int]:

@@ -57,7 +57,10 @@
  *                           row's fields as rows of the selected schema (fury_schema_select)
  *                           (FMT/row/binary/writer/BinaryWriter.java:161-212,243-245,
  *                            FMT/row/binary/writer/BinaryRowWriter.java:86-129)
- *   fury_rows_to_arrow     ArrowWriter.write(row)* + finishAsRecordBatch
+ *   fury_row_zip            the same writer calls fed from the getters of several BinaryRows: the fields
+ *                           of up to four batches joined row by row, as rows of the zipped schema
+ *                           (fury_schema_zip)
+ *   fury_rows_to_arrow    ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
  *                           (FMT/vectorized/ArrowWriter.java:74-99)
@@ -538,6 +541,58 @@ int fury_schema_select(const fury_schema* schema, const int32_t* fields, int32_t
 int fury_row_select(const fury_schema* schema, const int32_t* fields, int32_t num_selected,
                     const void* rows, const int64_t* row_offsets, int64_t nrows,
                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+
+/* The fields of several row batches joined row by row -- fury_row_select generalised from one source
+ * to several: add a computed column to existing rows, replace a field of any type, re-join two halves
+ * that were processed separately.  Per row it is the getters of several BinaryRows feeding one fresh
+ * BinaryRowWriter of the combined schema, with the writer calls fury_row_select names; a
+ * variable-length value addresses everything below it relative to its own base, so it moves into
+ * another row as its bytes and one rewritten slot, whichever row it came from.
+ *
+ * Picks (both functions, same rules, each message prefixed with the function's name): 1 <= num_sources
+ * <= FURY_ZIP_MAX_SOURCES row schemas; picks holds 2 * num_picks int32 words, pick j = (source index,
+ * top-level slot of that source), num_picks >= 1 with no upper limit, in any order, the same (source,
+ * slot) pair at most once.  A source that no pick names is allowed and is never read (its rows and
+ * row_offsets may be NULL).  A null table, a count out of range, a source index outside [0,
+ * num_sources), a slot outside its source or a duplicate pair returns FURY_ERR_INVALID_ARGUMENT; a
+ * collection schema among the sources returns FURY_ERR_UNSUPPORTED.
+ *
+ * fury_schema_zip: the row schema of the picked fields in pick order (names, types, nullability and
+ * children kept; info, hash and node count equal fury_schema_create of those fields; equal names from
+ * different sources are kept as they are).  The caller destroys it.  Host only.
+ *
+ * fury_row_zip: output row r holds, in slot j, field picks[j] of row r of its source; every source has
+ * nrows rows.  With B, F, bm and total those of the pick's source s (row_offsets NULL or ignored when
+ * that source is_fixed: row r at r * F_s) and n', bm', F' those of the zipped schema, each picked field
+ * follows rules 2-4 of fury_row_select unchanged.  Rule 1 holds per source: if row r of source s
+ * starts off an 8-byte boundary, its header leaves [0, total_s) or its own extent is shorter than F_s,
+ * every field picked from s is null in output row r (bit set, slot 0, no payload), the fields of the
+ * other sources are unaffected, and FURY_ERR_OUT_OF_BOUNDS names row r.  W starts at F' and advances in
+ * pick order across all sources; should it exceed INT32_MAX - 7 the whole output row is all null, as
+ * in fury_row_select.  out_offsets, out_rows, out_capacity, the measure form (out_rows == NULL), the
+ * fixed form (a zipped schema that is_fixed: row r at r * F', out_offsets may be NULL, FURY_ERR_CAPACITY
+ * before any device work when the buffer is too small; otherwise out_offsets is required) and nrows ==
+ * 0 are those of fury_row_select; the output is canonical for any input.
+ * Consequences: with one source, the output and the reported rows equal fury_row_select of the same
+ * slots, for any input bytes; for rows any writer made, the output equals fury_row_encode of the picked
+ * columns under the zipped schema byte for byte; zipping fury_row_select(A, S1) and fury_row_select(A,
+ * S2) with the picks that restore A's field order returns A's bytes.
+ * Every rows and out_rows is 8-byte aligned; out_rows must not overlap any source, sources may alias
+ * each other.  Nothing outside [rows_s, rows_s + total_s) of a source is read and nothing outside
+ * [out_rows, out_rows + min(out_capacity, needed)) and out_offsets is written.  Asynchronous on
+ * `stream`, no host synchronisation; argument errors are returned before any device work, a pending
+ * device error of the stream first. */
+#define FURY_ZIP_MAX_SOURCES 4
+typedef struct fury_zip_source {
+  const fury_schema* schema;     /* a row schema (not a collection schema) */
+  const void* rows;              /* device, 8-byte aligned */
+  const int64_t* row_offsets;    /* nrows + 1 entries; ignored (may be NULL) when schema is_fixed */
+} fury_zip_source;
+int fury_schema_zip(const fury_schema* const* schemas, int32_t num_sources,
+                    const int32_t* picks, int32_t num_picks, fury_schema** out);
+int fury_row_zip(const fury_zip_source* sources, int32_t num_sources,
+                 const int32_t* picks, int32_t num_picks, int64_t nrows,
+                 void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
