@@ -96,6 +96,8 @@ SIGNATURES = {
                                        ctypes.POINTER(_P)]),
     "fury_row_zip": (ctypes.c_int, [ctypes.POINTER(FuryZipSource), _I32, ctypes.POINTER(_I32), _I32,
                                     _I64, _P, _I64, _P, _P]),
+    "fury_row_implode": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
+    "fury_row_wrap": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "fury_schema_num_nodes": (_I32, [_P]),
     "fury_decode_prepare": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(_I64),
                                            ctypes.POINTER(_I64), ctypes.POINTER(_P), _P]),

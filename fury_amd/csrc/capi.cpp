@@ -1493,6 +1493,133 @@ int fury_row_explode(const fury_schema* s, const int32_t* path, int32_t path_len
   return launch_explode(a, hs);
 }
 
+// The checks fury_row_implode and fury_row_wrap share, after their schema checks; fills what both set.
+static int implode_args(const OwnedField& value, const void* values, const int64_t* value_offsets,
+                        int64_t num_values, int64_t nrows, void* out_rows, int64_t out_capacity,
+                        int64_t* out_offsets, const std::string& f, ImplodeArgs* a) {
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (num_values < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_values < 0");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(values, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values must be 8-byte aligned");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (!value_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_offsets is null");
+  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
+  if (misaligned(value_offsets, 8) || misaligned(out_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": value_offsets / out_offsets must be 8-byte aligned");
+  if (num_values > 0 && !values) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values is null");
+  *a = ImplodeArgs{};
+  a->values = static_cast<const uint8_t*>(values);
+  a->value_offsets = value_offsets;
+  a->num_values = num_values;
+  a->nrows = nrows;
+  a->out = static_cast<uint8_t*>(out_rows);
+  a->cap = out_rows ? out_capacity : 0;
+  a->out_offsets = out_offsets;
+  a->least = 8;                       // [int64 numElements] / [int64 keyArrayBytes]
+  if (value.type_id == FURY_TYPE_STRUCT) {
+    const int64_t m = static_cast<int64_t>(value.children.size());
+    a->least = static_cast<int32_t>(bitmap_bytes(m) + 8 * m);
+  }
+  return FURY_OK;
+}
+
+static bool is_nested(int32_t type_id) {
+  return type_id == FURY_TYPE_STRUCT || type_id == FURY_TYPE_LIST || type_id == FURY_TYPE_MAP;
+}
+
+// Element rows back into LIST values (implode.hip): BinaryArrayWriter.reset(n) + write(ordinal,
+// BinaryRow | BinaryArray | BinaryMap) over a batch, inside a one-field row or as the array itself.
+int fury_row_implode(const fury_schema* s, const void* values, const int64_t* value_offsets,
+                     int64_t num_values, const int64_t* list_offsets, int64_t nrows,
+                     const uint8_t* entry_validity, const uint8_t* elem_validity,
+                     int64_t num_elements, void* out_rows, int64_t out_capacity,
+                     int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_implode");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (s->root == 0 && s->num_fields != 1)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a row schema of " + std::to_string(s->num_fields) + " fields: the target "
+                         "is a row schema with exactly one LIST field (join further fields with "
+                         "fury_row_zip)");
+  const OwnedField& list = s->fields[0];
+  if (list.type_id == FURY_TYPE_MAP)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": the target " + list.name + " is a MAP: assembling a map needs a scalar "
+                         "key array, which fury_row_explode does not produce");
+  if (list.type_id != FURY_TYPE_LIST)
+    return set_error(FURY_ERR_UNSUPPORTED, f + ": the target " + list.name + " is not a LIST");
+  const OwnedField& elem = list.children[0];
+  if (!is_nested(elem.type_id))
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": the elements of " + list.name + " are not STRUCT, LIST or MAP: such a list "
+                         "encodes from a flat child column through fury_row_encode");
+  if (s->root != 0 && entry_validity)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": entry_validity with a collection schema: an array entry is never null");
+  if (num_elements < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_elements < 0");
+  if (!list_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": list_offsets is null");
+  if (misaligned(list_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": list_offsets must be 8-byte aligned");
+  if (misaligned(entry_validity, 4) || misaligned(elem_validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": entry_validity / elem_validity must be 4-byte aligned");
+  ImplodeArgs a;
+  int st = implode_args(elem, values, value_offsets, num_values, nrows, out_rows, out_capacity,
+                        out_offsets, f, &a);
+  if (st) return st;
+  st = take_device_error(hs);
+  if (st) return st;
+  a.list_offsets = list_offsets;
+  a.entry_validity = reinterpret_cast<const uint32_t*>(entry_validity);
+  a.elem_validity = reinterpret_cast<const uint32_t*>(elem_validity);
+  a.num_elements = num_elements;
+  a.prefix = s->root == 0 ? 16 : 0;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_implode(a, hs);
+}
+
+// Nested values back into one-field rows (implode.hip): BinaryRowWriter.write(0, BinaryRow |
+// BinaryArray | BinaryMap) over a batch.
+int fury_row_wrap(const fury_schema* s, const void* values, const int64_t* value_offsets,
+                  int64_t num_values, const uint8_t* validity, int64_t nrows, void* out_rows,
+                  int64_t out_capacity, int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_wrap");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a collection schema: the target is a row schema with exactly one field");
+  if (s->num_fields != 1)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a row schema of " + std::to_string(s->num_fields) + " fields: the target "
+                         "is a row schema with exactly one field (join further fields with "
+                         "fury_row_zip)");
+  const OwnedField& value = s->fields[0];
+  if (!is_nested(value.type_id))
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": the target " + value.name + " is not a STRUCT, LIST or MAP");
+  if (misaligned(validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": validity must be 4-byte aligned");
+  ImplodeArgs a;
+  int st = implode_args(value, values, value_offsets, num_values, nrows, out_rows, out_capacity,
+                        out_offsets, f, &a);
+  if (st) return st;
+  st = take_device_error(hs);
+  if (st) return st;
+  a.elem_validity = reinterpret_cast<const uint32_t*>(validity);
+  a.num_elements = nrows;
+  a.prefix = 16;
+  a.wrap = 1;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_implode(a, hs);
+}
+
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,
                         int64_t nrows, int64_t* node_entries, int64_t* node_bytes,
                         fury_decode_plan** plan, void* stream) {

@@ -457,6 +457,40 @@ static_assert(sizeof(ZipArgs) <= 4096, "ZipArgs must fit the kernel argument blo
 // `table`: the nwords words described above (host); copied into the argument block or uploaded.
 int launch_zip(const ZipArgs& a, const int32_t* table, int nwords, hipStream_t stream);
 
+// ---- element rows back into lists, nested values back into rows: implode.hip ---------------------
+// BinaryArrayWriter.reset(n) + write(ordinal, BinaryRow | BinaryArray | BinaryMap) over a batch, and a
+// one-field BinaryRowWriter around the array (prefix 16) or around a single value (wrap): the inverses
+// of launch_explode and launch_extract.  values / value_offsets: a compact batch of num_values values
+// (value_offsets[num_values] = VT); a present element -- elem_validity bit 1, NULL: all -- takes the
+// value whose index is the rank of its bit.  Value check: 0 <= start <= end <= VT, start and size
+// multiples of 8, size >= least, index < num_values; a value that fails makes its element (wrap: its
+// row) null and raises kErrBounds with the output row, unless that row is null by entry_validity.
+// Row r owns elements [list_offsets[r], list_offsets[r + 1]), which must lie in [0, num_elements] in
+// order and number at most (INT32_MAX - 15) / 8, and its array (plus prefix) must not exceed INT32_MAX
+// - 7: otherwise the row is null (prefix 16) or an empty array (prefix 0) and raises kErrBounds.  wrap:
+// list_offsets and entry_validity are NULL, num_elements = nrows, row r owns element r and has no array
+// header.  Nothing outside [0, VT) of values is read; out NULL: the measure form; bytes at or past
+// `cap` are never written while out_offsets is always complete.  Asynchronous on `stream`.
+struct ImplodeArgs {
+  const uint8_t* values;
+  const int64_t* value_offsets;       // num_values + 1 entries
+  int64_t num_values;
+  const int64_t* list_offsets;        // nrows + 1 entries; wrap: NULL
+  int64_t nrows;
+  const uint32_t* entry_validity;     // optional, rows form only
+  const uint32_t* elem_validity;      // optional; wrap: the rows' validity
+  int64_t num_elements;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t least;                      // STRUCT: the child's fixed_size; LIST / MAP: 8
+  int32_t prefix;                     // 16: rows form and wrap ([bitmap][slot]); 0: collection form
+  int32_t wrap;
+  int32_t pad_;
+};
+int launch_implode(const ImplodeArgs& a, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

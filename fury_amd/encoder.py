@@ -1325,6 +1325,206 @@ class RowEncoder:
         out = RowBatch(rows[:total], offs[:count + 1], count, child.schema_hash)
         return (out, lo, ev[:(n + 7) // 8], valid[:(E + 7) // 8], par[:count], ords[:count])
 
+    # -- elements and nested values back into rows (BinaryArrayWriter / BinaryRowWriter.write of a
+    #    nested value over a batch): the inverses of explode and extract ---------------------------
+    def field_encoder(self, name) -> "RowEncoder":
+        """The one-field ``RowEncoder`` of the field ``name`` (a name or slot index), cached: the
+        target of ``implode`` / ``wrap`` for that field, and what ``with_fields`` takes back."""
+        return self.selected_encoder([name])
+
+    def _value_encoder(self, wrap: bool):
+        """The encoder of the values ``wrap`` (the field) / ``implode`` (the LIST's elements) take,
+        or None when this encoder is no target: the library then says why."""
+        key = "_wrap_values" if wrap else "_implode_values"
+        if key not in self.__dict__:
+            f = self._schema.fields
+            node = f[0] if len(f) == 1 and (not wrap or not self._schema.collection) else None
+            if node is not None and not wrap:
+                node = node.children[0] if node.type_id == LIST else None
+            self.__dict__[key] = (
+                None if node is None or node.type_id not in (STRUCT, LIST, MAP) else
+                RowEncoder(node.children, self.device) if node.type_id == STRUCT else
+                ArrayEncoder(node, self.device) if node.type_id == LIST else
+                MapEncoder(node, self.device))
+        return self.__dict__[key]
+
+    def _value_args(self, values: RowBatch, wrap: bool, stream, keep: list):
+        """(values, value_offsets, num_values) of a compact batch of values."""
+        child = self._value_encoder(wrap)
+        if child is not None:
+            child._check_hash(values)
+        vo = values.row_offsets
+        if vo is None:                         # fixed-width rows: row i at i * fixed_size
+            size = child._schema.fixed_size if child is not None else 0
+            with _on(stream):
+                vo = torch.arange(values.nrows + 1, dtype=torch.int64, device=self.device) * size
+            keep.append(vo)
+        rows = values.rows
+        if rows.numel() == 0:                  # every value empty: still a pointer, never read
+            with _on(stream):
+                rows = torch.empty(16, dtype=torch.uint8, device=self.device)
+            keep.append(rows)
+        return _ptr(rows), _ptr(vo), vo.numel() - 1
+
+    def _bitmap_words(self, bits, count: Optional[int], stream, keep: list):
+        """``bits`` as the device bitmap the kernels read (see ``_mask_words``; a uint8 bitmap that
+        is no whole number of 32-bit words is copied into one that is) and the number of bits a
+        ``count`` of None stands for: a bool tensor's entries, a bitmap's 8 per byte."""
+        if bits is None:
+            return None, count
+        if bits.dtype == torch.bool:
+            n = bits.numel()
+            words = self._mask_words(bits, n, stream)
+        else:
+            n = 8 * bits.numel()
+            words = bits
+            if bits.numel() % 4:
+                with _on(stream):
+                    words = torch.zeros((bits.numel() + 3) // 4 * 4, dtype=torch.uint8,
+                                        device=self.device)
+                    words[:bits.numel()] = bits
+        keep.append(words)
+        return words, n if count is None else count
+
+    def _implode_args(self, elements: RowBatch, list_offsets, entry_validity, elem_validity,
+                      num_elements, out_rows, out_offsets, stream, keep: list):
+        vals = self._value_args(elements, False, stream, keep)
+        nrows = list_offsets.numel() - 1
+        ev, _ = self._bitmap_words(entry_validity, nrows, stream, keep)
+        lv, num_elements = self._bitmap_words(elem_validity, num_elements, stream, keep)
+        if num_elements is None:               # every element present: as many as there are values
+            num_elements = elements.nrows
+        return (self._schema.handle, *vals, _ptr(list_offsets), nrows, _ptr(ev), _ptr(lv),
+                int(num_elements), _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets),
+                _stream_handle(stream))
+
+    def implode_into(self, elements: RowBatch, list_offsets: torch.Tensor,
+                     out_rows: Optional[torch.Tensor], out_offsets: torch.Tensor,
+                     entry_validity: Optional[torch.Tensor] = None,
+                     elem_validity: Optional[torch.Tensor] = None,
+                     num_elements: Optional[int] = None, stream=None) -> None:
+        """The inverse of ``explode``, on the TARGET encoder -- a one-field encoder whose field is a
+        LIST of STRUCT / LIST / MAP (``field_encoder(name)``: output row r is a row holding the list)
+        or the ``ArrayEncoder`` of such a list (output entry r is the array; no ``entry_validity``).
+        ``elements`` is the compact batch of element values ``explode`` returned (processed or not),
+        ``list_offsets`` (int64, nrows + 1 entries) the Arrow list offsets, ``entry_validity`` /
+        ``elem_validity`` (optional; device bitmaps, LSB-first, or bool tensors) the rows that have
+        a list and the elements that are not null: a present element takes the next value in
+        order.  ``num_elements`` defaults to the bits of ``elem_validity`` (a bool tensor's entries,
+        8 per byte of a bitmap) or, without one, to ``elements.nrows``.  One call, no host
+        synchronisation; ``out_offsets`` (int64, nrows + 1 entries), capacity and ``out_rows=None``
+        as in ``take_into``; a malformed value or range comes out null and is reported by
+        ``device_status(stream)``.  ``out_rows`` must not overlap ``elements.rows``."""
+        keep: list = []
+        _check(N.lib().fury_row_implode(*self._implode_args(
+            elements, list_offsets, entry_validity, elem_validity, num_elements, out_rows,
+            out_offsets, stream, keep)))
+
+    def bind_implode(self, elements: RowBatch, list_offsets: torch.Tensor,
+                     out_rows: Optional[torch.Tensor], out_offsets: torch.Tensor,
+                     entry_validity: Optional[torch.Tensor] = None,
+                     elem_validity: Optional[torch.Tensor] = None,
+                     num_elements: Optional[int] = None, stream=None):
+        """``implode_into`` bound like ``bind_explode``: pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_implode
+        args = self._implode_args(elements, list_offsets, entry_validity, elem_validity,
+                                  num_elements, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, elements, list_offsets, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def implode(self, elements: RowBatch, list_offsets: torch.Tensor,
+                entry_validity: Optional[torch.Tensor] = None,
+                elem_validity: Optional[torch.Tensor] = None,
+                num_elements: Optional[int] = None, stream=None) -> RowBatch:
+        """``implode_into`` into a new batch of this encoder: measured on the device (one host read
+        of the byte total), then written."""
+        child = self._value_encoder(False)
+        if child is not None:
+            child._check_hash(elements)
+        n = list_offsets.numel() - 1
+        with _on(stream):
+            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            args = (elements, list_offsets)
+            kw = dict(entry_validity=entry_validity, elem_validity=elem_validity,
+                      num_elements=num_elements, stream=stream)
+            self.implode_into(*args, None, offs, **kw)
+            total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.implode_into(*args, rows, offs, **kw)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, self.schema_hash)
+
+    def _wrap_args(self, values: RowBatch, validity, nrows, out_rows, out_offsets, stream,
+                   keep: list):
+        vals = self._value_args(values, True, stream, keep)
+        bits, nrows = self._bitmap_words(validity, nrows, stream, keep)
+        if nrows is None:                      # every row present: as many as there are values
+            nrows = values.nrows
+        return (self._schema.handle, *vals, _ptr(bits), int(nrows), _ptr(out_rows),
+                _nbytes(out_rows), _ptr(out_offsets), _stream_handle(stream))
+
+    def wrap_into(self, values: RowBatch, out_rows: Optional[torch.Tensor],
+                  out_offsets: torch.Tensor, validity: Optional[torch.Tensor] = None,
+                  nrows: Optional[int] = None, stream=None) -> None:
+        """The inverse of ``extract``, on the TARGET encoder -- a one-field encoder whose field is a
+        STRUCT, LIST or MAP (``field_encoder(name)``): output row r holds the next value of the
+        compact batch ``values`` when its ``validity`` bit (optional; device bitmap, LSB-first, or
+        bool tensor) is 1, else a null field.  ``nrows`` defaults like ``implode_into``'s
+        ``num_elements``.  One call, no host synchronisation; outputs as in ``implode_into``."""
+        keep: list = []
+        _check(N.lib().fury_row_wrap(*self._wrap_args(values, validity, nrows, out_rows, out_offsets,
+                                                      stream, keep)))
+
+    def bind_wrap(self, values: RowBatch, out_rows: Optional[torch.Tensor],
+                  out_offsets: torch.Tensor, validity: Optional[torch.Tensor] = None,
+                  nrows: Optional[int] = None, stream=None):
+        """``wrap_into`` bound like ``bind_extract``: pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_wrap
+        args = self._wrap_args(values, validity, nrows, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, values, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def wrap(self, values: RowBatch, validity: Optional[torch.Tensor] = None,
+             nrows: Optional[int] = None, stream=None) -> RowBatch:
+        """``wrap_into`` into a new batch of this encoder: measured on the device (one host read of
+        the byte total), then written."""
+        keep: list = []
+        n = self._wrap_args(values, validity, nrows, None, None, stream, keep)[5]
+        with _on(stream):
+            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            self.wrap_into(values, None, offs, validity, n, stream)
+            total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.wrap_into(values, rows, offs, validity, n, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, self.schema_hash)
+
+    def with_elements(self, batch: RowBatch, name, elements: RowBatch, list_offsets: torch.Tensor,
+                      entry_validity: Optional[torch.Tensor] = None,
+                      elem_validity: Optional[torch.Tensor] = None, stream=None):
+        """``batch`` with its LIST field ``name`` rebuilt from ``elements`` (``implode`` on
+        ``field_encoder(name)``, then ``with_fields``): explode, process the elements, put them
+        back.  Returns ``(encoder, batch)`` of the result."""
+        enc = self.field_encoder(name)
+        lists = enc.implode(elements, list_offsets, entry_validity, elem_validity, stream=stream)
+        return self.with_fields(batch, enc, lists, stream)
+
+    def with_nested(self, batch: RowBatch, name, values: RowBatch,
+                    validity: Optional[torch.Tensor] = None, stream=None):
+        """``batch`` with its STRUCT / LIST / MAP field ``name`` replaced by ``values`` (``wrap`` on
+        ``field_encoder(name)``, then ``with_fields``).  Returns ``(encoder, batch)``."""
+        enc = self.field_encoder(name)
+        rows = enc.wrap(values, validity, batch.nrows, stream)
+        return self.with_fields(batch, enc, rows, stream)
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""

@@ -60,6 +60,13 @@
  *   fury_row_zip            the same writer calls fed from the getters of several BinaryRows: the fields
  *                           of up to four batches joined row by row, as rows of the zipped schema
  *                           (fury_schema_zip)
+ *   fury_row_implode        BinaryArrayWriter.reset(n) + write(ordinal, BinaryRow | BinaryArray |
+ *                           BinaryMap) / setNullAt over a batch: element rows back into the LIST of
+ *                           every row, the inverse of fury_row_explode
+ *                           (FMT/row/binary/writer/BinaryArrayWriter.java:91-129,
+ *                            FMT/row/binary/writer/BinaryWriter.java:106-114,243-245)
+ *   fury_row_wrap           BinaryRowWriter.write(0, BinaryRow | BinaryArray | BinaryMap) over a batch:
+ *                           nested values back into one-field rows, the inverse of fury_row_extract
  *   fury_rows_to_arrow    ArrowWriter.write(row)* + finishAsRecordBatch
  *                           (FMT/vectorized/ArrowWriter.java:74-99,205-225,519-540)
  *   fury_arrow_append       ArrowWriter.write(row) appending at rowCount until finish() / reset()
@@ -593,6 +600,89 @@ int fury_schema_zip(const fury_schema* const* schemas, int32_t num_sources,
 int fury_row_zip(const fury_zip_source* sources, int32_t num_sources,
                  const int32_t* picks, int32_t num_picks, int64_t nrows,
                  void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+
+/* Elements and nested values back into rows -- the inverses of fury_row_explode and fury_row_extract.
+ * A nested row, array or map addresses everything below it relative to its own base, so re-nesting a
+ * value is a copy of its bytes plus a small generated header: per row the batch form of
+ * BinaryArrayWriter.reset(n) followed by write(ordinal, BinaryRow | BinaryArray | BinaryMap) or
+ * setNullAt(ordinal) (FMT/row/binary/writer/BinaryArrayWriter.java:91-129,
+ * FMT/row/binary/writer/BinaryWriter.java:106-114,243-245; cpp/fury/row/writer.cc), and of a one-field
+ * BinaryRowWriter.write(0, BinaryRow | BinaryArray | BinaryMap).  With fury_row_zip the loop closes on
+ * the device, as bytes: explode -> process the elements -> implode -> zip back into the parent rows.
+ *
+ * Target (`schema` is the TARGET's schema; each message is prefixed with the function's name):
+ *   - fury_row_implode, rows form: a row schema with exactly one field, a LIST of STRUCT / LIST / MAP;
+ *     output row r is [8-byte bitmap][slot][array];
+ *   - fury_row_implode, collection form: a LIST collection schema (fury_collection_schema_create) with
+ *     such an element; output entry r is the array itself and entry_validity must be NULL
+ *     (FURY_ERR_INVALID_ARGUMENT);
+ *   - fury_row_wrap: a row schema with exactly one field, a STRUCT, LIST or MAP;
+ *   - FURY_ERR_UNSUPPORTED: a row schema with more than one field (join further fields with
+ *     fury_row_zip); a scalar / STRING / BINARY / DECIMAL element or value; a MAP as implode's target
+ *     (assembling a map needs a scalar key array, which fury_row_explode does not produce); a
+ *     collection schema as wrap's target.
+ *
+ * Inputs of both: values / value_offsets (num_values + 1 device int64) are a compact batch of values in
+ * order -- exactly what fury_row_explode and fury_row_extract write to out_rows / out_offsets;
+ * VT = value_offsets[num_values] is the buffer's length.  num_values = explode's elem_capacity is
+ * valid: the entries past the count repeat the total and are never referenced.  value_offsets is always
+ * required.  Validity bitmaps are Arrow bitmaps, LSB-first, 1 = present, READ as whole 32-bit words
+ * (4-byte aligned, readable to a multiple of 4 bytes; bits at or past the count are ignored), NULL =
+ * all present.  A present element (implode) or row (wrap) takes the next value in order: its value
+ * index v is the rank of its bit, the number of 1 bits before it in the whole bitmap.
+ *
+ * Value check: value v is well-formed when v < num_values, 0 <= value_offsets[v] <= value_offsets[v + 1]
+ * <= VT, start and size are multiples of 8 and size >= least -- a STRUCT's fixed_size (bitmap + 8 per
+ * field), 8 for a LIST or MAP.  A value that fails makes its element (implode) or row (wrap) null,
+ * none of its bytes are copied, and FURY_ERR_OUT_OF_BOUNDS is reported on `stream`
+ * (fury_device_status) naming the output row.
+ *
+ * fury_row_implode, per row r with n = list_offsets[r + 1] - list_offsets[r] (list_offsets: nrows + 1
+ * device int64, the Arrow list offsets fury_row_explode wrote; elements are numbered [0, num_elements)):
+ *   1. the row fails unless 0 <= list_offsets[r] <= list_offsets[r + 1] <= num_elements and
+ *      n <= (INT32_MAX - 15) / 8 (BinaryArrayWriter's MAX_ROUNDED_ARRAY_LENGTH rule);
+ *   2. array bytes, bm = ((n + 63) / 64) * 8: int64 n; bm bitmap bytes, bit i = 1 when element i is
+ *      null (its elem_validity bit is 0 or its value failed), bits at or past n 0; n slots, 0 for a null
+ *      element, else (off << 32) | size with off relative to the array's base; then the present
+ *      elements' bytes back to back in ordinal order from 8 + bm + 8 n;
+ *   3. the array's size A = 8 + bm + 8 n + the kept value bytes; the row fails if 16 + A (rows form) or
+ *      A (collection form) exceeds INT32_MAX - 7;
+ *   4. rows form, row present: bitmap word 0, slot (16 << 32) | A, array; the row's size is 16 + A;
+ *   5. rows form, row null (entry_validity bit 0) or failed: 16 bytes, bit 0 set, slot 0.  A failed
+ *      row is reported; a null row is not, whatever its list_offsets range holds and whichever values
+ *      its elements would have taken;
+ *   6. collection form, row failed: an empty array (8 bytes, n = 0), reported;
+ *   7. ranks always count over the whole elem_validity, also through null and failed rows, and a value
+ *      no present row's range covers is never reported.
+ *
+ * fury_row_wrap, per row r: a present row (validity bit 1) whose value passes the value check and has
+ * 16 + size <= INT32_MAX - 7 gives [bitmap word 0][(16 << 32) | size][the value's bytes]; a null or
+ * failed row gives 16 bytes with bit 0 set and slot 0 (failed: reported).
+ *
+ * Both: out_offsets[0 .. nrows] (required) is the exclusive scan of the sizes; out_rows, out_capacity
+ * and the measure form (out_rows == NULL) behave exactly as in fury_row_take: bytes at or past the
+ * capacity are never written, out_offsets is always complete.  nrows == 0 writes out_offsets[0] = 0.
+ * Asynchronous on `stream`, no host synchronisation; a pending device error of the stream is returned
+ * first; argument errors (null or misaligned pointers, negative counts or capacity) are returned
+ * before any device work; nrows or num_elements of 2^38 or more is FURY_ERR_INVALID_ARGUMENT.
+ * `values` and `out_rows` are 8-byte aligned and must not overlap.  Nothing outside [values, values +
+ * VT), the given bitmaps and the given offsets arrays is read; nothing outside [out_rows, out_rows +
+ * min(out_capacity, needed)) and out_offsets is written.
+ * Consequences, for rows any writer made: implode(explode(X, {f})) in rows form equals
+ * fury_row_select(X, {f}) byte for byte; in collection form it equals fury_row_extract(X, {f}) when no
+ * row is null; wrap(extract(X, {f})) equals fury_row_select(X, {f}); each equals fury_row_encode of the
+ * same columns under the target schema.  For any input the output is canonical: zero null slots, zero
+ * bitmap bits at or past n. */
+int fury_row_implode(const fury_schema* schema,
+                     const void* values, const int64_t* value_offsets, int64_t num_values,
+                     const int64_t* list_offsets, int64_t nrows,
+                     const uint8_t* entry_validity, const uint8_t* elem_validity,
+                     int64_t num_elements,
+                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+int fury_row_wrap(const fury_schema* schema,
+                  const void* values, const int64_t* value_offsets, int64_t num_values,
+                  const uint8_t* validity, int64_t nrows,
+                  void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
