@@ -98,6 +98,11 @@ SIGNATURES = {
                                     _I64, _P, _I64, _P, _P]),
     "fury_row_implode": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P]),
     "fury_row_wrap": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    "fury_schema_map_side": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _I32,
+                                            ctypes.POINTER(_P)]),
+    "fury_row_map_split": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
+                                          _P, _I64, _P, _P, _P, _P, _P]),
+    "fury_row_map_join": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "fury_schema_num_nodes": (_I32, [_P]),
     "fury_decode_prepare": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(_I64),
                                            ctypes.POINTER(_I64), ctypes.POINTER(_P), _P]),

@@ -272,6 +272,11 @@ int take_device_error(hipStream_t stream) {
                      "an earlier asynchronous launch failed on the device (a decoupled look-back "
                      "gave up waiting): the outputs of that call are invalid");
   }
+  if (oob && !(oob_at >> 63) && (oob_at & kErrCounts))     // fury_row_map_split / fury_row_map_join
+    return set_error(FURY_ERR_OUT_OF_BOUNDS,
+                     "decode: " + where_text(oob_at & ~kErrCounts) +
+                         " has map key and value arrays of different element counts "
+                         "(BinaryMap.pointTo); the outputs of that call are invalid");
   if (oob)
     return set_error(FURY_ERR_OUT_OF_BOUNDS,
                      "decode: " + where_text(oob_at) +
@@ -1618,6 +1623,122 @@ int fury_row_wrap(const fury_schema* s, const void* values, const int64_t* value
   st = device_error_word(hs, &a.err);
   if (st) return st;
   return launch_implode(a, hs);
+}
+
+// A map's key and value arrays as two batches (map.hip): BinaryMap.keyArray / valueArray over a batch.
+// The path is resolved on the host (schema.cpp).
+int fury_row_map_split(const fury_schema* s, const int32_t* path, int32_t path_len, const void* rows,
+                       const int64_t* row_offsets, int64_t nrows, void* out_keys,
+                       int64_t key_capacity, int64_t* out_key_offsets, void* out_values,
+                       int64_t value_capacity, int64_t* out_value_offsets, int64_t* out_count,
+                       int64_t* out_indices, uint8_t* out_validity, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_map_split");
+  MapPath p;
+  int st = resolve_map_path(s, path, path_len, f, &p);
+  if (st) return st;
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (key_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": key_capacity < 0");
+  if (value_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_capacity < 0");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (misaligned(out_keys, 8) || misaligned(out_values, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_keys / out_values must be 8-byte aligned");
+  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
+  if (!out_key_offsets && !out_value_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": out_key_offsets and out_value_offsets are both null: no side is wanted");
+  if ((out_keys && !out_key_offsets) || (out_values && !out_value_offsets))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": out_keys / out_values without its offsets (a side whose offsets are null "
+                         "is skipped: its buffer must be null too)");
+  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
+  if (misaligned(row_offsets, 8) || misaligned(out_key_offsets, 8) || misaligned(out_value_offsets, 8) ||
+      misaligned(out_count, 8) || misaligned(out_indices, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": row_offsets / out_key_offsets / out_value_offsets / out_count / out_indices "
+                         "must be 8-byte aligned");
+  if (misaligned(out_validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_validity must be 4-byte aligned");
+  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  st = take_device_error(hs);
+  if (st) return st;
+  MapSplitArgs a{};
+  a.rows = static_cast<const uint8_t*>(rows);
+  a.row_offsets = row_offsets;
+  a.nrows = nrows;
+  a.keys = MapSide{static_cast<uint8_t*>(out_keys), out_keys ? key_capacity : 0, out_key_offsets,
+                   element_width(p.map->children[0].type_id)};
+  a.vals = MapSide{static_cast<uint8_t*>(out_values), out_values ? value_capacity : 0,
+                   out_value_offsets, element_width(p.map->children[1].type_id)};
+  a.out_count = out_count;
+  a.out_indices = out_indices;
+  a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
+  a.nlevels = s->root != 0 ? 0 : path_len;
+  a.min_size = 8;
+  a.exact = 0;
+  for (int32_t k = 0; k < a.nlevels; k++) {
+    a.nfields[k] = p.path.nfields[k];
+    a.slot[k] = path[k];
+  }
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_map_split(a, hs);
+}
+
+// Two array batches back into maps (map.hip): BinaryMap(keys, values, field) over a batch, inside a
+// one-field row or as the map itself.
+int fury_row_map_join(const fury_schema* s, const void* keys, const int64_t* key_offsets,
+                      const void* values, const int64_t* value_offsets, int64_t num_values,
+                      const uint8_t* validity, int64_t nrows, void* out_rows, int64_t out_capacity,
+                      int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_map_join");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (s->root == 0 && s->num_fields != 1)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": a row schema of " + std::to_string(s->num_fields) + " fields: the target "
+                         "is a row schema with exactly one MAP field (join further fields with "
+                         "fury_row_zip)");
+  const OwnedField& map = s->fields[0];
+  if (map.type_id != FURY_TYPE_MAP)
+    return set_error(FURY_ERR_UNSUPPORTED, f + ": the target " + map.name + " is not a MAP");
+  if (s->root != 0 && validity)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": validity with a collection schema: a map entry is never null");
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (num_values < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_values < 0");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(keys, 8) || misaligned(values, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": keys / values must be 8-byte aligned");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (!key_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": key_offsets is null");
+  if (!value_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_offsets is null");
+  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
+  if (misaligned(key_offsets, 8) || misaligned(value_offsets, 8) || misaligned(out_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": key_offsets / value_offsets / out_offsets must be 8-byte aligned");
+  if (misaligned(validity, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": validity must be 4-byte aligned");
+  if (num_values > 0 && !keys) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": keys is null");
+  if (num_values > 0 && !values) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values is null");
+  int st = take_device_error(hs);
+  if (st) return st;
+  MapJoinArgs a{};
+  a.keys = static_cast<const uint8_t*>(keys);
+  a.key_offsets = key_offsets;
+  a.values = static_cast<const uint8_t*>(values);
+  a.value_offsets = value_offsets;
+  a.num_values = num_values;
+  a.validity = reinterpret_cast<const uint32_t*>(validity);
+  a.nrows = nrows;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  a.prefix = s->root == 0 ? 16 : 0;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_map_join(a, hs);
 }
 
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,

@@ -1,4 +1,4 @@
-// extract_dev.h -- what extract.hip (fury_row_extract) and explode.hip (fury_row_explode) share: the
+// extract_dev.h -- what extract.hip (fury_row_extract) and explode.hip (fury_row_explode), implode.hip and map.hip share: the
 // walk along a path of struct slots, and the compact step that turns per-tile ballots and per-lane
 // (source start, size) pairs into a dense batch.  The designs are described in the two .hip files.
 #pragma once
@@ -56,6 +56,18 @@ __device__ __forceinline__ bool walk_path(const Args& a, int64_t r, int64_t tota
   *size_out = size;
   *bad_out = bad;
   return live;
+}
+
+// Bits [64 t, 64 t + 64) of an Arrow bitmap of n bits read as 32-bit words (NULL: all set); bits at or
+// past n are 0.  64 t < n.
+__device__ __forceinline__ uint64_t tile_word(const uint32_t* bits, int64_t t, int64_t n) {
+  uint64_t w = ~0ull;
+  if (bits) {
+    w = gl(bits)[2 * t];
+    if (64 * t + 32 < n) w |= static_cast<uint64_t>(gl(bits)[2 * t + 1]) << 32;
+  }
+  const int64_t rem = n - 64 * t;
+  return rem < 64 ? w & ((1ull << rem) - 1) : w;
 }
 
 // The tile ballot of a locate pass: count, mask and the two validity words of tile t of an output of

@@ -54,18 +54,6 @@ constexpr int kTileWaves = kTakeThreads / 64;     // element tiles per workgroup
 constexpr int64_t kMaxElems = (INT32_MAX - 15) / 8;      // BinaryArrayWriter.MAX_ROUNDED_ARRAY_LENGTH
 constexpr int64_t kMaxSize = INT32_MAX - 7;
 
-// Bits [64 t, 64 t + 64) of an Arrow bitmap of n bits read as 32-bit words (NULL: all set); bits at or
-// past n are 0.  64 t < n.
-__device__ __forceinline__ uint64_t tile_word(const uint32_t* bits, int64_t t, int64_t n) {
-  uint64_t w = ~0ull;
-  if (bits) {
-    w = gl(bits)[2 * t];
-    if (64 * t + 32 < n) w |= static_cast<uint64_t>(gl(bits)[2 * t + 1]) << 32;
-  }
-  const int64_t rem = n - 64 * t;
-  return rem < 64 ? w & ((1ull << rem) - 1) : w;
-}
-
 __global__ __launch_bounds__(kTakeThreads) void implode_rank(const uint32_t* __restrict__ bits,
                                                              int64_t n, int64_t nt,
                                                              int64_t* __restrict__ tr) {

@@ -114,6 +114,18 @@ struct ExplodePath {
 int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
                          const std::string& f, ExplodePath* out);
 
+// The map fury_schema_map_side / fury_row_map_split work on (schema.cpp; rules and messages in
+// include/fury_row.h): the MAP a path reaches in a row schema, or the field of a MAP collection schema
+// (path_len 0).
+struct MapPath {
+  ExtractPath path;                   // row schema: the walk to the MAP; else empty
+  const OwnedField* map = nullptr;
+};
+int resolve_map_path(const fury_schema* s, const int32_t* path, int32_t path_len,
+                     const std::string& f, MapPath* out);
+// The slot width of an array's elements: the scalar's width, 8 for a variable-length or nested one.
+int32_t element_width(int32_t type_id);
+
 // The selection rules fury_schema_select and fury_row_select share (schema.cpp; rules and messages in
 // include/fury_row.h): top-level slots of a row schema, any order, no duplicates, no count limit.
 int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t num_selected,

@@ -491,6 +491,66 @@ struct ImplodeArgs {
 };
 int launch_implode(const ImplodeArgs& a, hipStream_t stream);
 
+// ---- maps as key / value arrays and back: map.hip --------------------------------------------------
+// BinaryMap.keyArray() / valueArray() over a batch: the map of row r is the MAP value the path reaches
+// (the members the walk reads are ExtractArgs', min_size = 8) or, for a collection schema (nlevels 0),
+// the batch entry itself; its two BinaryArrays go, unchanged, into two compact batches shaped like
+// launch_extract's outputs with one shared count / indices / validity.  Bounds = "Decode bounds"
+// above: the map header, keyArrayBytes (>= 0, a multiple of 8, 8 + kb <= size), both arrays >= 8 bytes,
+// equal element counts n >= 0 and, per side, 8 + bitmap + round8(n * width) inside the array; nothing
+// below the two array headers is read.  A map that fails is null and raises kErrBounds with its source
+// row (kErrCounts set in the location when the counts differ).  A side whose out_offsets is NULL is
+// skipped; out NULL: the measure form.  Asynchronous on `stream`.
+constexpr uint64_t kErrCounts = 1ull << 62;       // in a kErrBounds row location: key / value counts differ
+struct MapSide {
+  uint8_t* out;                       // NULL: the measure form
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries; NULL: the side is skipped
+  int64_t width;                      // slot width of the side's elements (8: variable-length / nested)
+};
+struct MapSplitArgs {
+  const uint8_t* rows;
+  const int64_t* row_offsets;
+  int64_t nrows;
+  MapSide keys, vals;
+  int64_t* out_count;
+  int64_t* out_indices;               // optional, nrows entries
+  uint32_t* out_validity;             // optional, (nrows + 31) / 32 words
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t nlevels;                    // 0 (collection schema) .. kMaxNestLevels
+  int32_t min_size;                   // 8
+  int32_t exact;                      // 0
+  int32_t pad_;
+  int32_t nfields[64];                // kMaxNestLevels
+  int32_t slot[64];
+};
+int launch_map_split(const MapSplitArgs& a, hipStream_t stream);
+// The constructor BinaryMap(keys, values, field) / serializeForMap over a batch: [int64 key array
+// bytes][key array][value array], inside a one-field row (prefix 16) or as the map itself (prefix 0).
+// keys / values: two compact batches of num_values entries each; a present row -- validity bit 1, NULL:
+// all -- takes entry v of both, v the rank of its bit.  Each entry passes ImplodeArgs' value check with
+// least 8 against its own buffer's length, the int64 counts at the two starts are equal and in [0,
+// (INT32_MAX - 15) / 8], and prefix + 8 + both sizes <= INT32_MAX - 7: otherwise the row is null (prefix
+// 16) or the empty map (prefix 0) and raises kErrBounds.  Nothing outside the two buffers' lengths is
+// read; out NULL: the measure form; bytes at or past `cap` are never written while out_offsets is
+// always complete.  Asynchronous on `stream`.
+struct MapJoinArgs {
+  const uint8_t* keys;
+  const int64_t* key_offsets;         // num_values + 1 entries
+  const uint8_t* values;
+  const int64_t* value_offsets;       // num_values + 1 entries
+  int64_t num_values;
+  const uint32_t* validity;           // optional, rows form only
+  int64_t nrows;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // nrows + 1 entries
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+  int32_t prefix;                     // 16: rows form ([bitmap][slot]); 0: collection form
+  int32_t pad_;
+};
+int launch_map_join(const MapJoinArgs& a, hipStream_t stream);
+
 // ---- generic (nested) schema engine: generic.hip --------------------------------------------
 constexpr int kGenMaxNodes = 48;      // schema tree nodes in the argument block
 constexpr int kGenMaxWideNodes = 4096;  // beyond 48: node table uploaded per call (GenArgs.tab)

@@ -253,6 +253,35 @@ int resolve_explode_path(const fury_schema* s, const int32_t* path, int32_t path
   return FURY_OK;
 }
 
+int resolve_map_path(const fury_schema* s, const int32_t* path, int32_t path_len,
+                     const std::string& f, MapPath* out) {
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  *out = MapPath{};
+  if (s->root != 0) {
+    if (path_len != 0)
+      return set_error(FURY_ERR_INVALID_ARGUMENT,
+                       f + ": path_len " + std::to_string(path_len) + " with a collection schema: "
+                           "every entry is the map itself, path_len must be 0");
+    out->map = &s->fields[0];
+  } else {
+    const int st = resolve_extract_path(s, path, path_len, f, &out->path);
+    if (st) return st;
+    out->map = out->path.end;
+  }
+  if (out->map->type_id != FURY_TYPE_MAP)
+    return set_error(FURY_ERR_UNSUPPORTED,
+                     f + ": " + (s->root != 0 ? "the collection" :
+                                 "path[" + std::to_string(path_len - 1) + "]") + " (" + out->map->name +
+                         ", " + type_name(out->map->type_id) + ") is not a MAP: only a map has a key "
+                         "and a value array");
+  return FURY_OK;
+}
+
+int32_t element_width(int32_t type_id) {
+  const int32_t w = type_width(type_id);
+  return w < 0 ? 8 : w;               // BinaryArrayWriter ctor :71-82
+}
+
 int check_field_selection(const fury_schema* s, const int32_t* fields, int32_t nsel,
                           const std::string& f) {
   if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
@@ -553,6 +582,30 @@ int fury_schema_element(const fury_schema* s, const int32_t* path, int32_t path_
     return fury_schema_create(top.data(), static_cast<int32_t>(top.size()), out);
   }
   const std::vector<OwnedField> one{*p.elem};         // lives until the schema has copied it
+  c_fields(one, &top, &keep);
+  return fury_collection_schema_create(top.data(), out);
+}
+
+int fury_schema_map_side(const fury_schema* s, const int32_t* path, int32_t path_len, int32_t side,
+                         fury_schema** out) {
+  const std::string f("fury_schema_map_side");
+  if (!out) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out is null");
+  *out = nullptr;
+  MapPath p;
+  int st = resolve_map_path(s, path, path_len, f, &p);
+  if (st) return st;
+  if (side != 0 && side != 1)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": side " + std::to_string(side) + " is not 0 (the key array) or 1 (the "
+                         "value array)");
+  OwnedField list;                    // the LIST field whose element is the map's key / value field
+  list.name = p.map->name;
+  list.type_id = FURY_TYPE_LIST;
+  list.nullable = p.map->nullable;
+  list.children.push_back(p.map->children[side]);
+  const std::vector<OwnedField> one{list};            // lives until the schema has copied it
+  std::vector<fury_field> top;
+  std::vector<std::vector<fury_field>> keep;
   c_fields(one, &top, &keep);
   return fury_collection_schema_create(top.data(), out);
 }

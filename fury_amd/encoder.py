@@ -1525,6 +1525,191 @@ class RowEncoder:
         rows = enc.wrap(values, validity, batch.nrows, stream)
         return self.with_fields(batch, enc, rows, stream)
 
+    # -- maps as key / value arrays and back (BinaryMap.keyArray / valueArray and the constructor
+    #    BinaryMap(keys, values, field) over a batch) ------------------------------------------------
+    def _map_side_encoder(self, path, side: int) -> "ArrayEncoder":
+        idx = self._path(() if path is None else path)
+        cache = self.__dict__.setdefault("_map_sides", {})
+        enc = cache.get((tuple(idx), side))
+        if enc is None:
+            sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+            h = ctypes.c_void_p()              # the library checks the path: its rules, its messages
+            _check(N.lib().fury_schema_map_side(self._schema.handle, sel, len(idx), side,
+                                                ctypes.byref(h)))
+            N.lib().fury_schema_destroy(h)
+            fields = self._schema.fields
+            node = fields[0]                   # a collection schema: its one field
+            for k in idx:
+                node, fields = fields[k], fields[k].children
+            enc = ArrayEncoder(Field(node.name, LIST, node.nullable, (node.children[side],)),
+                               self.device)
+            cache[(tuple(idx), side)] = enc
+        return enc
+
+    def key_array_encoder(self, path) -> "ArrayEncoder":
+        """The ``ArrayEncoder`` of the key arrays of the MAP field ``path`` reaches (see ``_path``),
+        cached: the codec of the first batch ``split_map`` returns."""
+        return self._map_side_encoder(path, 0)
+
+    def value_array_encoder(self, path) -> "ArrayEncoder":
+        """The ``ArrayEncoder`` of the value arrays of the MAP field ``path``: the codec of the
+        second batch ``split_map`` returns."""
+        return self._map_side_encoder(path, 1)
+
+    def _split_map_args(self, batch: RowBatch, path, out_keys, out_key_offsets, out_values,
+                        out_value_offsets, out_count, out_indices, out_validity, stream, keep: list):
+        self._check_hash(batch)
+        idx = self._path(() if path is None else path)
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        return (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, _ptr(out_keys), _nbytes(out_keys), _ptr(out_key_offsets),
+                _ptr(out_values), _nbytes(out_values), _ptr(out_value_offsets), _ptr(out_count),
+                _ptr(out_indices), _ptr(out_validity), _stream_handle(stream))
+
+    def split_map_into(self, batch: RowBatch, path, out_keys: Optional[torch.Tensor],
+                       out_key_offsets: Optional[torch.Tensor],
+                       out_values: Optional[torch.Tensor],
+                       out_value_offsets: Optional[torch.Tensor], out_count: torch.Tensor,
+                       out_indices: Optional[torch.Tensor] = None,
+                       out_validity: Optional[torch.Tensor] = None, stream=None) -> None:
+        """The key array and the value array of the MAP field ``path`` (see ``_path``) of every row
+        of ``batch``, packed in row order into ``out_keys`` / ``out_values`` as batches of
+        ``key_array_encoder(path)`` / ``value_array_encoder(path)``: one call, no host
+        synchronisation.  Both batches have the same entries: ``out_count``, ``out_indices`` and
+        ``out_validity`` are shared and each side has its own offsets (int64, nrows + 1 entries),
+        capacity and measure form (buffer None), all as in ``extract_into``.  A side whose offsets
+        are None is skipped.  A malformed map counts as null and is reported by
+        ``device_status(stream)``."""
+        keep: list = []
+        _check(N.lib().fury_row_map_split(*self._split_map_args(
+            batch, path, out_keys, out_key_offsets, out_values, out_value_offsets, out_count,
+            out_indices, out_validity, stream, keep)))
+
+    def bind_split_map(self, batch: RowBatch, path, out_keys: Optional[torch.Tensor],
+                       out_key_offsets: Optional[torch.Tensor],
+                       out_values: Optional[torch.Tensor],
+                       out_value_offsets: Optional[torch.Tensor], out_count: torch.Tensor,
+                       out_indices: Optional[torch.Tensor] = None,
+                       out_validity: Optional[torch.Tensor] = None, stream=None):
+        """``split_map_into`` bound like ``bind_extract``: path and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_map_split
+        args = self._split_map_args(batch, path, out_keys, out_key_offsets, out_values,
+                                    out_value_offsets, out_count, out_indices, out_validity, stream,
+                                    keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_keys, out_key_offsets, out_values, out_value_offsets,
+                     out_count, out_indices, out_validity, self, self._schema)
+        return call
+
+    def split_map(self, batch: RowBatch, path, stream=None):
+        """``(keys, values, indices, validity)`` of the MAP field ``path``: the key arrays and the
+        value arrays of the non-null maps as two batches of ``key_array_encoder(path)`` /
+        ``value_array_encoder(path)`` (schema_hash 0), their row numbers (int64) and the Arrow
+        bitmap (uint8, LSB-first) of the rows that have a map.  Located and measured on the device,
+        count and byte totals come back in one host read, then both sides are copied in one call."""
+        self._check_hash(batch)
+        idx = self._path(() if path is None else path)
+        n = batch.nrows
+        with _on(stream):
+            head = torch.empty(3, dtype=torch.int64, device=self.device)      # count, key / value bytes
+            ko = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            vo = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            src = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)[:n]
+            valid = torch.zeros(((n + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
+            into = lambda k, v, *opt: RowEncoder.split_map_into(                 # noqa: E731
+                self, batch, idx, k, ko, v, vo, head[:1], *opt, stream=stream)
+            into(None, None)
+            head[1:2] = ko[n:]
+            head[2:] = vo[n:]
+            count, kt, vt = (int(x) for x in head.cpu())
+            keys = torch.empty(max(kt, 16), dtype=torch.uint8, device=self.device)
+            vals = torch.empty(max(vt, 16), dtype=torch.uint8, device=self.device)
+        into(keys, vals, src if n else None, valid if n else None)
+        self.device_status(stream)
+        return (RowBatch(keys[:kt], ko[:count + 1], count, 0),
+                RowBatch(vals[:vt], vo[:count + 1], count, 0), src[:count], valid[:(n + 7) // 8])
+
+    def _join_map_args(self, keys: RowBatch, values: RowBatch, validity, nrows, out_rows,
+                       out_offsets, stream, keep: list):
+        for b in (keys, values):
+            if b.schema_hash != 0:
+                raise ClassNotCompatibleException(
+                    f"join_map takes two array batches (schema hash 0), not one of hash "
+                    f"{b.schema_hash}")
+        if keys.nrows != values.nrows:
+            raise IllegalArgumentException(
+                f"join_map: {keys.nrows} key arrays and {values.nrows} value arrays")
+        ptrs = []
+        for b in (keys, values):
+            rows = b.rows
+            if rows.numel() == 0:              # no entries: still a pointer, never read
+                with _on(stream):
+                    rows = torch.empty(16, dtype=torch.uint8, device=self.device)
+                keep.append(rows)
+            ptrs += [_ptr(rows), _ptr(b.row_offsets)]
+        bits, nrows = self._bitmap_words(validity, nrows, stream, keep)
+        if nrows is None:                      # every row present: as many as there are entries
+            nrows = keys.nrows
+        return (self._schema.handle, *ptrs, keys.row_offsets.numel() - 1, _ptr(bits), int(nrows),
+                _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets), _stream_handle(stream))
+
+    def join_map_into(self, keys: RowBatch, values: RowBatch, out_rows: Optional[torch.Tensor],
+                      out_offsets: torch.Tensor, validity: Optional[torch.Tensor] = None,
+                      nrows: Optional[int] = None, stream=None) -> None:
+        """The inverse of ``split_map``, on the TARGET encoder -- a one-field encoder whose field is
+        a MAP (``field_encoder(name)``: output row r is a row holding the map) or the ``MapEncoder``
+        of such a map (output entry r is the map; no ``validity``).  ``keys`` / ``values`` are the
+        two compact array batches ``split_map`` returned (processed or not, with the same number of
+        entries); output row r takes the next entry of both when its ``validity`` bit (optional;
+        device bitmap, LSB-first, or bool tensor) is 1, else it holds a null field.  ``nrows``
+        defaults like ``wrap_into``'s.  One call, no host synchronisation; outputs as in
+        ``implode_into``; a malformed entry or two arrays of different element counts come out null
+        and are reported by ``device_status(stream)``.  ``out_rows`` must overlap neither input."""
+        keep: list = []
+        _check(N.lib().fury_row_map_join(*self._join_map_args(keys, values, validity, nrows, out_rows,
+                                                              out_offsets, stream, keep)))
+
+    def bind_join_map(self, keys: RowBatch, values: RowBatch, out_rows: Optional[torch.Tensor],
+                      out_offsets: torch.Tensor, validity: Optional[torch.Tensor] = None,
+                      nrows: Optional[int] = None, stream=None):
+        """``join_map_into`` bound like ``bind_wrap``: pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_map_join
+        args = self._join_map_args(keys, values, validity, nrows, out_rows, out_offsets, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, keys, values, out_rows, out_offsets, self, self._schema)
+        return call
+
+    def join_map(self, keys: RowBatch, values: RowBatch, validity: Optional[torch.Tensor] = None,
+                 nrows: Optional[int] = None, stream=None) -> RowBatch:
+        """``join_map_into`` into a new batch of this encoder: measured on the device (one host read
+        of the byte total), then written."""
+        keep: list = []
+        n = self._join_map_args(keys, values, validity, nrows, None, None, stream, keep)[7]
+        with _on(stream):
+            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            self.join_map_into(keys, values, None, offs, validity, n, stream)
+            total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.join_map_into(keys, values, rows, offs, validity, n, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, self.schema_hash)
+
+    def with_map(self, batch: RowBatch, name, keys: RowBatch, values: RowBatch,
+                 validity: Optional[torch.Tensor] = None, stream=None):
+        """``batch`` with its MAP field ``name`` rebuilt from the array batches ``keys`` and
+        ``values`` (``join_map`` on ``field_encoder(name)``, then ``with_fields``): split, process
+        either side, put them back.  Returns ``(encoder, batch)`` of the result."""
+        enc = self.field_encoder(name)
+        maps = enc.join_map(keys, values, validity, batch.nrows, stream)
+        return self.with_fields(batch, enc, maps, stream)
+
     def device_status(self, stream=None) -> None:
         """Synchronises ``stream`` and raises FuryDeviceError if an earlier asynchronous call's
         kernel could not produce a valid result (``fury_device_status``)."""
@@ -1904,6 +2089,40 @@ class MapEncoder(_CollectionEncoder):
 
     def value_field(self) -> Field:
         return self._field.children[1]
+
+    # -- every entry as its key array and its value array, and back: RowEncoder's methods with the
+    #    empty path / in collection form --------------------------------------------------------------
+    def key_array_encoder(self) -> "ArrayEncoder":
+        """The ``ArrayEncoder`` of this map's key arrays: see ``RowEncoder.key_array_encoder``."""
+        return RowEncoder.key_array_encoder(self, ())
+
+    def value_array_encoder(self) -> "ArrayEncoder":
+        return RowEncoder.value_array_encoder(self, ())
+
+    def split_into(self, batch: RowBatch, *outs, **kw) -> None:
+        """``RowEncoder.split_map_into`` without the path: every batch entry is the map."""
+        RowEncoder.split_map_into(self, batch, (), *outs, **kw)
+
+    def bind_split(self, batch: RowBatch, *outs, **kw):
+        return RowEncoder.bind_split_map(self, batch, (), *outs, **kw)
+
+    def split(self, batch: RowBatch, stream=None):
+        """``RowEncoder.split_map`` without the path: the key and value arrays of every entry."""
+        return RowEncoder.split_map(self, batch, (), stream)
+
+    def join_into(self, keys: RowBatch, values: RowBatch, out_rows: Optional[torch.Tensor],
+                  out_offsets: torch.Tensor, stream=None) -> None:
+        """``RowEncoder.join_map_into`` in collection form: output entry r is the map of entry r of
+        ``keys`` and ``values`` (a map entry is never null: no validity)."""
+        RowEncoder.join_map_into(self, keys, values, out_rows, out_offsets, stream=stream)
+
+    def bind_join(self, keys: RowBatch, values: RowBatch, out_rows: Optional[torch.Tensor],
+                  out_offsets: torch.Tensor, stream=None):
+        return RowEncoder.bind_join_map(self, keys, values, out_rows, out_offsets, stream=stream)
+
+    def join(self, keys: RowBatch, values: RowBatch, stream=None) -> RowBatch:
+        """``RowEncoder.join_map`` in collection form, into a new batch of this encoder."""
+        return RowEncoder.join_map(self, keys, values, stream=stream)
 
     def to_map(self, pairs: list) -> bytes:
         return self._bytes(pairs)

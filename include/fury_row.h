@@ -619,8 +619,9 @@ int fury_row_zip(const fury_zip_source* sources, int32_t num_sources,
  *   - fury_row_wrap: a row schema with exactly one field, a STRUCT, LIST or MAP;
  *   - FURY_ERR_UNSUPPORTED: a row schema with more than one field (join further fields with
  *     fury_row_zip); a scalar / STRING / BINARY / DECIMAL element or value; a MAP as implode's target
- *     (assembling a map needs a scalar key array, which fury_row_explode does not produce); a
- *     collection schema as wrap's target.
+ *     (assembling a map needs a scalar key array, which fury_row_explode does not produce: build the
+ *     value array with implode's collection form and put it next to a key array with
+ *     fury_row_map_join); a collection schema as wrap's target.
  *
  * Inputs of both: values / value_offsets (num_values + 1 device int64) are a compact batch of values in
  * order -- exactly what fury_row_explode and fury_row_extract write to out_rows / out_offsets;
@@ -683,6 +684,109 @@ int fury_row_wrap(const fury_schema* schema,
                   const void* values, const int64_t* value_offsets, int64_t num_values,
                   const uint8_t* validity, int64_t nrows,
                   void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+
+/* Maps as key / value arrays and back -- BinaryMap.keyArray() / valueArray()
+ * (FMT/row/binary/BinaryMap.java:62-77,101-108) and the constructor BinaryMap(BinaryArray keys,
+ * BinaryArray values, Field) (BinaryMap.java:52-60; the writer side is serializeForMap:
+ * writeDirectly(-1), the key array, writeDirectly(offset, keyArraySize), the value array) over a batch.
+ * A map is [int64 keyArrayBytes][key BinaryArray][value BinaryArray] and each array addresses its
+ * contents relative to its own base, so both directions are byte copies plus one generated 8-byte
+ * word.  An array batch is a batch under a LIST collection schema: fury_row_encode /
+ * fury_decode_prepare encode and decode it (scalar, STRING or DECIMAL keys), fury_row_explode /
+ * fury_row_implode in collection form take it (STRUCT / LIST / MAP values).  With them every map shape
+ * is processable on the device: split -> (decode + re-encode the key array, or explode -> process ->
+ * implode the value array) -> join -> fury_row_zip.
+ *
+ * Which map (fury_schema_map_side and fury_row_map_split, same rules, each message prefixed with the
+ * function's name): `schema` is a row schema and `path` follows fury_row_extract's rules and must end at
+ * a MAP, or `schema` is a MAP collection schema and path_len is 0 (else FURY_ERR_INVALID_ARGUMENT; path
+ * may be NULL).  A path that ends at a STRUCT or LIST, or a LIST collection schema, returns
+ * FURY_ERR_UNSUPPORTED.
+ *
+ * fury_schema_map_side: the LIST collection schema of the key array (side 0) or the value array (side
+ * 1; any other value returns FURY_ERR_INVALID_ARGUMENT) -- info, node count and hash (0) equal
+ * fury_collection_schema_create of a LIST field (the map's name and nullability) whose element is the
+ * map's key / value field.  The caller destroys it.  Host only.
+ *
+ * fury_row_map_split, per row r with total = row_offsets[nrows]:
+ *   1. the path is walked exactly as fury_row_explode's steps 1-2 walk it, collection form included,
+ *      giving the map's span [V, V + size), size >= 8, or null, or a failure;
+ *   2. kb = (int32) of the 8 bytes at V (BinaryMap.pointTo); the row fails unless kb >= 0, kb % 8 == 0
+ *      and 8 + kb <= size;
+ *   3. the key array is K = [V + 8, V + 8 + kb), the value array A = [V + 8 + kb, V + size); the row
+ *      fails unless both are >= 8 bytes;
+ *   4. n_k, n_v = (int32) of the int64 at the start of each array; the row fails unless
+ *      n_k == n_v >= 0 (BinaryMap.pointTo:73-75);
+ *   5. per side the row fails unless 8 + ((n + 63) / 64) * 8 + round_up_8(n * w) <= that array's size,
+ *      w the element's slot width (fury_type_width; 8 for a variable-length or nested element);
+ *   6. nothing below the two array headers is read or checked: the arrays move as bytes, and
+ *      validating them any deeper belongs to whatever decodes them;
+ *   7. a null row has no entry and no error;
+ *   8. a failed row has no entry and FURY_ERR_OUT_OF_BOUNDS is reported on `stream`
+ *      (fury_device_status) naming row r; a failure of n_k == n_v reports the same status and its
+ *      message says that the element counts differ.
+ * Outputs are shaped like fury_row_extract's, one batch per side: *out_count, out_indices and
+ * out_validity (whole 32-bit words) are shared -- entry validity is decided on both headers, so the two
+ * batches always have the same entries --; per side nrows + 1 offsets (entries [0, count] the exclusive
+ * scan of the array sizes, entries (count, nrows] repeating the total), the arrays back to back, its own
+ * capacity and its own measure form (out_keys / out_values NULL with its offsets given), all exactly
+ * as fury_row_extract's out_rows / out_capacity / out_offsets.  A side whose offsets pointer is NULL is
+ * skipped (its buffer must be NULL too) and never read beyond its header; both sides NULL returns
+ * FURY_ERR_INVALID_ARGUMENT.  nrows == 0 writes *out_count = 0 and [0] = 0 of each given offsets array.
+ *
+ * fury_row_map_join: `schema` is the TARGET's schema, in the two forms of fury_row_implode --
+ *   - rows form: a row schema with exactly one field, a MAP; output row r is [bitmap word
+ *     0][(16 << 32) | M][map];
+ *   - collection form: a MAP collection schema; output entry r is the map itself and validity must be
+ *     NULL (FURY_ERR_INVALID_ARGUMENT);
+ *   - FURY_ERR_UNSUPPORTED: a row schema with more than one field (join further fields with
+ *     fury_row_zip); a field or collection that is not a MAP.
+ * keys / key_offsets and values / value_offsets are two compact batches of num_values entries each --
+ * exactly what fury_row_map_split writes; KT = key_offsets[num_values] and VT =
+ * value_offsets[num_values] are the buffers' lengths.  validity is one Arrow bitmap read as
+ * fury_row_wrap reads it (whole 32-bit words, NULL = all present).  Per row r:
+ *   1. a present row takes entry v of BOTH batches, v the rank of its bit;
+ *   2. each of the two entries must pass fury_row_implode's value check with least = 8, against its own
+ *      buffer's length: v < num_values, 0 <= start <= end <= KT (VT), start and size multiples of 8,
+ *      size >= 8;
+ *   3. n_k, n_v = the int64 at each entry's start must be equal and in [0, (INT32_MAX - 15) / 8]
+ *      (BinaryArrayWriter's MAX_ROUNDED_ARRAY_LENGTH); nothing else of an entry is checked;
+ *   4. with ksz, vsz the entries' sizes, M = 8 + ksz + vsz; the row fails if 16 + M (rows form) or M
+ *      (collection form) exceeds INT32_MAX - 7;
+ *   5. a present, well-formed row writes the map: int64 ksz, the key entry's bytes, the value entry's
+ *      bytes;
+ *   6. rows form, row null (validity bit 0) or failed: 16 bytes, bit 0 set, slot 0.  A failed row is
+ *      reported (FURY_ERR_OUT_OF_BOUNDS naming row r, saying so when the counts differ); a null row is
+ *      not;
+ *   7. collection form, row failed: the empty map, 24 bytes (int64 8, int64 0, int64 0), reported.
+ * out_offsets, out_rows, out_capacity, the measure form, nrows == 0, the argument errors, the
+ * asynchrony and the read / write extents are fury_row_wrap's, with [keys, keys + KT) and [values,
+ * values + VT) for its one input buffer; neither input buffer may overlap out_rows (they may alias
+ * each other).
+ *
+ * Consequences, for rows any writer made: join(split(X, {m})) in rows form equals fury_row_select(X,
+ * {m}) byte for byte; in collection form it equals fury_row_extract(X, {m}) when no row is null; each
+ * side of split(X) equals fury_row_encode, under that side's collection schema, of the map column's key
+ * / value child with the map's offsets; fury_row_explode(X, path, side) equals fury_row_explode in
+ * collection form (side 0) of split's batch for that side.
+ * Both: asynchronous on `stream`, no host synchronisation; a pending device error of the stream is
+ * returned first; argument errors (null or misaligned pointers, negative counts or capacities) are
+ * returned before any device work; nrows of 2^38 or more is FURY_ERR_INVALID_ARGUMENT.  Every buffer is
+ * 8-byte aligned and no output overlaps an input; split reads nothing outside [rows, rows + total),
+ * and neither writes outside [out, out + min(capacity, needed)) of a buffer and the given arrays. */
+int fury_schema_map_side(const fury_schema* schema, const int32_t* path, int32_t path_len,
+                         int32_t side, fury_schema** out);
+int fury_row_map_split(const fury_schema* schema, const int32_t* path, int32_t path_len,
+                       const void* rows, const int64_t* row_offsets, int64_t nrows,
+                       void* out_keys, int64_t key_capacity, int64_t* out_key_offsets,
+                       void* out_values, int64_t value_capacity, int64_t* out_value_offsets,
+                       int64_t* out_count, int64_t* out_indices, uint8_t* out_validity,
+                       void* stream);
+int fury_row_map_join(const fury_schema* schema,
+                      const void* keys, const int64_t* key_offsets,
+                      const void* values, const int64_t* value_offsets, int64_t num_values,
+                      const uint8_t* validity, int64_t nrows,
+                      void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
 /* Appends the Arrow columns `src` (src_rows top-level entries, e.g. fury_rows_to_arrow /
  * fury_decode_execute output) at entry dst_rows of the columns `dst` -- ArrowWriter.write(row)
