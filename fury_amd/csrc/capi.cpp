@@ -725,6 +725,86 @@ int gen_measure(const fury_schema* s, const fury_column* cols, int64_t nrows, in
   return st;
 }
 
+// Words [0, 3) of a selected field's table entry (SelectArgs in kernels.h): the slot, the width and the
+// size rule of top-level field k of `s`; whether the field is variable-length.
+bool selection_words(const fury_schema* s, int32_t k, int32_t* t) {
+  const FieldPlan& p = s->plan[k];
+  t[0] = k;
+  t[2] = 0;
+  if (p.width > 0) {
+    t[1] = p.kind == kBool ? kSelBool : p.width;
+    return false;
+  }
+  t[1] = kSelVar;
+  switch (p.type_id) {
+    case FURY_TYPE_DECIMAL: t[2] = 16 | kSelExact; break;
+    case FURY_TYPE_STRUCT: {            // a row of the child's fields: at least its header
+      const int64_t m = static_cast<int64_t>(s->fields[k].children.size());
+      t[2] = static_cast<int32_t>(std::min<int64_t>(bitmap_bytes(m) + 8 * m, kSelNeed)) | kSelMod8;
+      break;
+    }
+    case FURY_TYPE_LIST:
+    case FURY_TYPE_MAP: t[2] = 8 | kSelMod8; break;      // [int64 numElements] / [int64 keyArrayBytes]
+    default: break;                     // STRING / BINARY: any size
+  }
+  return true;
+}
+
+// The selection table of fury_row_select (stride 4) and fury_row_zip (stride 5, SelectArgs / ZipArgs in
+// kernels.h): `stride` words per pick j of field_of(j) of schema_of(j) -- selection_words, then [3] its
+// index among the variable-length picks or -1 -- to which finish_selection appends those picks' j.
+struct Selection {
+  std::vector<int32_t> table;
+  std::vector<int32_t> var;           // the variable-length picks
+  int32_t out_bitmap = 0;
+  int64_t out_fixed = 0;              // the output row's header: its size when var is empty
+};
+template <class SchemaOf, class FieldOf>
+Selection make_selection(int32_t n, int stride, SchemaOf schema_of, FieldOf field_of) {
+  Selection sel;
+  sel.table.resize(static_cast<size_t>(stride) * n);
+  for (int32_t j = 0; j < n; j++) {
+    int32_t* t = &sel.table[static_cast<size_t>(stride) * j];
+    t[3] = -1;
+    if (!selection_words(schema_of(j), field_of(j), t)) continue;
+    t[3] = static_cast<int32_t>(sel.var.size());
+    sel.var.push_back(j);
+  }
+  sel.out_bitmap = bitmap_bytes(n);
+  sel.out_fixed = sel.out_bitmap + 8 * static_cast<int64_t>(n);
+  return sel;
+}
+
+// Rows of a fixed-width selection sit at r * out_fixed: the capacity is checked before the launch.
+int check_fixed_capacity(const Selection& sel, const void* out_rows, int64_t out_capacity,
+                         int64_t nrows, const std::string& f) {
+  if (!sel.var.empty() || !out_rows || out_capacity / sel.out_fixed >= nrows) return FURY_OK;
+  return set_error(FURY_ERR_CAPACITY,
+                   f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
+                       " rows of " + std::to_string(sel.out_fixed) + " bytes");
+}
+
+// What SelectArgs and ZipArgs say of the selection; the table is complete afterwards.
+template <class Args>
+void finish_selection(Selection* sel, int32_t n, Args* a) {
+  sel->table.insert(sel->table.end(), sel->var.begin(), sel->var.end());
+  a->nsel = n;
+  a->nvar = static_cast<int32_t>(sel->var.size());
+  a->out_bitmap_bytes = sel->out_bitmap;
+  a->out_fixed_size = static_cast<int32_t>(sel->out_fixed);
+}
+
+// The path of fury_row_extract / fury_row_explode / fury_row_map_split in their argument blocks, which
+// name the members alike (walk_path of extract_dev.h relies on that too).
+template <class Args>
+void set_path(Args* a, int32_t nlevels, const std::vector<int32_t>& nfields, const int32_t* path) {
+  a->nlevels = nlevels;
+  for (int32_t k = 0; k < nlevels; k++) {
+    a->nfields[k] = nfields[k];
+    a->slot[k] = path[k];
+  }
+}
+
 }  // namespace
 }  // namespace fury
 
@@ -1210,31 +1290,6 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
   return launch_filter(a, row_mask, out_count, out_indices, hs);
 }
 
-// Words [0, 3) of a selected field's table entry (SelectArgs in kernels.h): the slot, the width and the
-// size rule of top-level field k of `s`; whether the field is variable-length.
-static bool selection_words(const fury_schema* s, int32_t k, int32_t* t) {
-  const FieldPlan& p = s->plan[k];
-  t[0] = k;
-  t[2] = 0;
-  if (p.width > 0) {
-    t[1] = p.kind == kBool ? kSelBool : p.width;
-    return false;
-  }
-  t[1] = kSelVar;
-  switch (p.type_id) {
-    case FURY_TYPE_DECIMAL: t[2] = 16 | kSelExact; break;
-    case FURY_TYPE_STRUCT: {            // a row of the child's fields: at least its header
-      const int64_t m = static_cast<int64_t>(s->fields[k].children.size());
-      t[2] = static_cast<int32_t>(std::min<int64_t>(bitmap_bytes(m) + 8 * m, kSelNeed)) | kSelMod8;
-      break;
-    }
-    case FURY_TYPE_LIST:
-    case FURY_TYPE_MAP: t[2] = 8 | kSelMod8; break;      // [int64 numElements] / [int64 keyArrayBytes]
-    default: break;                     // STRING / BINARY: any size
-  }
-  return true;
-}
-
 // A subset of the fields, as rows (select.hip): BinaryRow's getters feeding a BinaryRowWriter of the
 // selected schema.  The host turns the selection into the int32 table SelectArgs describes.
 int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_selected,
@@ -1251,32 +1306,20 @@ int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_sel
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
   if (misaligned(row_offsets, 8) || misaligned(out_offsets, 8))
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets / out_offsets must be 8-byte aligned");
-  std::vector<int32_t> table(4 * static_cast<size_t>(num_selected));
-  std::vector<int32_t> var_fields;
-  for (int32_t j = 0; j < num_selected; j++) {
-    int32_t* t = &table[4 * static_cast<size_t>(j)];
-    t[3] = -1;
-    if (!selection_words(s, fields[j], t)) continue;
-    t[3] = static_cast<int32_t>(var_fields.size());
-    var_fields.push_back(j);
-  }
-  const bool sel_fixed = var_fields.empty();
-  const int32_t out_bitmap = bitmap_bytes(num_selected);
-  const int64_t out_fixed = out_bitmap + 8 * static_cast<int64_t>(num_selected);
+  Selection sel = make_selection(num_selected, 4, [&](int32_t) { return s; },
+                                 [&](int32_t j) { return fields[j]; });
   if (!s->is_fixed && !row_offsets)
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
-  if (!sel_fixed && !out_offsets)
+  if (!sel.var.empty() && !out_offsets)
     return set_error(FURY_ERR_INVALID_ARGUMENT,
                      f + ": a selection with a variable-length field needs out_offsets");
   if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  if (sel_fixed && out_rows && out_capacity / out_fixed < nrows)
-    return set_error(FURY_ERR_CAPACITY,
-                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
-                         " rows of " + std::to_string(out_fixed) + " bytes");
+  st = check_fixed_capacity(sel, out_rows, out_capacity, nrows, f);
+  if (st) return st;
   st = take_device_error(hs);
   if (st) return st;
-  table.insert(table.end(), var_fields.begin(), var_fields.end());
   SelectArgs a{};
+  finish_selection(&sel, num_selected, &a);
   a.rows = static_cast<const uint8_t*>(rows);
   a.row_offsets = s->is_fixed ? nullptr : row_offsets;    // fixed schemas: row i at i * fixed_size
   a.nrows = nrows;
@@ -1285,13 +1328,9 @@ int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_sel
   a.out_offsets = out_offsets;
   a.bitmap_bytes = s->bitmap_bytes;
   a.fixed_size = s->fixed_size;
-  a.nsel = num_selected;
-  a.nvar = static_cast<int32_t>(var_fields.size());
-  a.out_bitmap_bytes = out_bitmap;
-  a.out_fixed_size = static_cast<int32_t>(out_fixed);
   st = device_error_word(hs, &a.err);
   if (st) return st;
-  return launch_select(a, table.data(), static_cast<int>(table.size()), hs);
+  return launch_select(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
 }
 
 // The fields of several batches joined row by row (zip.hip): fury_row_select with a source per pick.
@@ -1311,18 +1350,12 @@ int fury_row_zip(const fury_zip_source* sources, int32_t num_sources, const int3
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
   if (misaligned(out_offsets, 8))
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets must be 8-byte aligned");
-  std::vector<int32_t> table(5 * static_cast<size_t>(num_picks));
-  std::vector<int32_t> var_picks;
+  Selection sel = make_selection(num_picks, 5, [&](int32_t j) { return schemas[picks[2 * j]]; },
+                                 [&](int32_t j) { return picks[2 * j + 1]; });
   uint32_t used = 0;
   for (int32_t j = 0; j < num_picks; j++) {
-    const int32_t s = picks[2 * j];
-    int32_t* t = &table[5 * static_cast<size_t>(j)];
-    t[3] = -1;
-    t[4] = s;
-    used |= 1u << s;
-    if (!selection_words(schemas[s], picks[2 * j + 1], t)) continue;
-    t[3] = static_cast<int32_t>(var_picks.size());
-    var_picks.push_back(j);
+    sel.table[5 * static_cast<size_t>(j) + 4] = picks[2 * j];     // the source word
+    used |= 1u << picks[2 * j];
   }
   for (int32_t s = 0; s < num_sources; s++) {       // a source no pick names is never read
     if (!((used >> s) & 1)) continue;
@@ -1336,22 +1369,17 @@ int fury_row_zip(const fury_zip_source* sources, int32_t num_sources, const int3
     if (nrows > 0 && !sources[s].rows)
       return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows is null");
   }
-  const bool zip_fixed = var_picks.empty();
-  const int32_t out_bitmap = bitmap_bytes(num_picks);
-  const int64_t out_fixed = out_bitmap + 8 * static_cast<int64_t>(num_picks);
-  if (out_fixed > INT32_MAX - 7)
+  if (sel.out_fixed > INT32_MAX - 7)
     return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the zipped row header exceeds 2 GiB");
-  if (!zip_fixed && !out_offsets)
+  if (!sel.var.empty() && !out_offsets)
     return set_error(FURY_ERR_INVALID_ARGUMENT,
                      f + ": picks with a variable-length field need out_offsets");
-  if (zip_fixed && out_rows && out_capacity / out_fixed < nrows)
-    return set_error(FURY_ERR_CAPACITY,
-                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
-                         " rows of " + std::to_string(out_fixed) + " bytes");
+  st = check_fixed_capacity(sel, out_rows, out_capacity, nrows, f);
+  if (st) return st;
   st = take_device_error(hs);
   if (st) return st;
-  table.insert(table.end(), var_picks.begin(), var_picks.end());
   ZipArgs a{};
+  finish_selection(&sel, num_picks, &a);
   for (int32_t s = 0; s < num_sources; s++) {
     if (!((used >> s) & 1)) continue;
     a.src[s].rows = static_cast<const uint8_t*>(sources[s].rows);
@@ -1364,14 +1392,10 @@ int fury_row_zip(const fury_zip_source* sources, int32_t num_sources, const int3
   a.out = static_cast<uint8_t*>(out_rows);
   a.cap = out_rows ? out_capacity : 0;
   a.out_offsets = out_offsets;
-  a.nsel = num_picks;
-  a.nvar = static_cast<int32_t>(var_picks.size());
-  a.out_bitmap_bytes = out_bitmap;
-  a.out_fixed_size = static_cast<int32_t>(out_fixed);
   a.used = used;
   st = device_error_word(hs, &a.err);
   if (st) return st;
-  return launch_zip(a, table.data(), static_cast<int>(table.size()), hs);
+  return launch_zip(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
 }
 
 // Nested values as batches (extract.hip): getStruct / getArray / getMap over a batch.  The path is
@@ -1412,13 +1436,9 @@ int fury_row_extract(const fury_schema* s, const int32_t* path, int32_t path_len
   a.out_count = out_count;
   a.out_indices = out_indices;
   a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
-  a.nlevels = path_len;
+  set_path(&a, path_len, p.nfields, path);
   a.min_size = p.min_size;
   a.exact = p.exact;
-  for (int32_t k = 0; k < path_len; k++) {
-    a.nfields[k] = p.nfields[k];
-    a.slot[k] = path[k];
-  }
   st = device_error_word(hs, &a.err);
   if (st) return st;
   return launch_extract(a, hs);
@@ -1482,17 +1502,13 @@ int fury_row_explode(const fury_schema* s, const int32_t* path, int32_t path_len
   a.out_parents = out_parents;
   a.out_ordinals = out_ordinals;
   a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
-  a.nlevels = s->root != 0 ? 0 : path_len;
+  set_path(&a, s->root != 0 ? 0 : path_len, p.path.nfields, path);
   a.min_size = 8;
   a.exact = 0;
   a.is_map = p.is_map;
   a.side = side;
   a.elem_min = p.elem_min;
   a.elem_exact = p.elem_exact;
-  for (int32_t k = 0; k < a.nlevels; k++) {
-    a.nfields[k] = p.path.nfields[k];
-    a.slot[k] = path[k];
-  }
   st = device_error_word(hs, &a.err);
   if (st) return st;
   return launch_explode(a, hs);
@@ -1673,13 +1689,9 @@ int fury_row_map_split(const fury_schema* s, const int32_t* path, int32_t path_l
   a.out_count = out_count;
   a.out_indices = out_indices;
   a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
-  a.nlevels = s->root != 0 ? 0 : path_len;
+  set_path(&a, s->root != 0 ? 0 : path_len, p.path.nfields, path);
   a.min_size = 8;
   a.exact = 0;
-  for (int32_t k = 0; k < a.nlevels; k++) {
-    a.nfields[k] = p.path.nfields[k];
-    a.slot[k] = path[k];
-  }
   st = device_error_word(hs, &a.err);
   if (st) return st;
   return launch_map_split(a, hs);

@@ -29,7 +29,8 @@
 //              with elements for rows.
 //   compact    device_scan of the tile counts, compact_entries of extract_dev.h (out_parents /
 //              out_ordinals are written here, the ordinal as element index - out_list_offsets[owner]),
-//              device_scan of the sizes, then copy_rows of take_dev.h.
+//              device_scan of the sizes, then extract's copy (extract_copy of extract_dev.h: copy_rows
+//              of take_dev.h over the compacted source starts).
 // Row bytes are read with plain loads in count and locate (headers and slots share cache lines with
 // the bytes the copy reads next); the copy's loads and stores are take_dev.h's non-temporal ones.
 // Bounds (ExplodeArgs, kernels.h): nothing outside [0, total) of the rows buffer is read, the output
@@ -191,14 +192,6 @@ __global__ __launch_bounds__(kTakeThreads) void explode_compact(const uint64_t* 
                   });
 }
 
-__global__ __launch_bounds__(kTakeThreads) void explode_copy(const uint8_t* __restrict__ rows,
-                                                             const int64_t* __restrict__ src,
-                                                             int64_t n, uint8_t* __restrict__ out,
-                                                             const int64_t* __restrict__ oo,
-                                                             int64_t cap) {
-  copy_rows(rows, [=](int64_t j) { return gl(src)[j]; }, n, out, oo, cap);
-}
-
 }  // namespace
 
 int launch_explode(const ExplodeArgs& a, hipStream_t stream) {
@@ -246,7 +239,7 @@ int launch_explode(const ExplodeArgs& a, hipStream_t stream) {
                        src, a.out_offsets);
     device_scan(a.out_offsets, cap, a.out_offsets + cap, sws, stream);
     if (copy)
-      hipLaunchKernelGGL(explode_copy, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a.rows,
+      hipLaunchKernelGGL(extract_copy, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a.rows,
                          src, cap, a.out, a.out_offsets, a.cap);
   }
   st = check_hip(hipGetLastError(), "explode launch");

@@ -20,8 +20,9 @@
 //              mask bits; entries at or past the count are filled by the lane of that position
 //              (-1 / size 0), so every entry is written exactly once (as filter_write of take.hip).
 //              device_scan of the sizes then makes out_offsets.
-//   copy       copy_rows of take_dev.h, the copy of take.hip, with the source start of output row j
-//              read from the compacted array.
+//   copy       extract_copy of extract_dev.h (explode.hip launches it too): copy_rows of take_dev.h,
+//              the copy of take.hip, with the source start of output row j read from the compacted
+//              array.
 // Bounds ("Decode bounds" of kernels.h, per level; ExtractArgs): nothing outside [0, total) of the
 // rows buffer is read, the output is written only inside [0, min(capacity, needed)).
 #include "extract_dev.h"
@@ -64,15 +65,6 @@ __global__ __launch_bounds__(kTakeThreads) void extract_compact(const uint64_t* 
   compact_entries(masks, loc, nrows, tc, count, src, oo,
                   [=](int64_t pos, int64_t r) { if (idx) gl(idx)[pos] = r; },
                   [=](int64_t r) { if (idx) gl(idx)[r] = -1; });
-}
-
-// n output rows at oo[0..n] (oo[n] = bytes needed); output row j = the bytes at src[j].
-__global__ __launch_bounds__(kTakeThreads) void extract_copy(const uint8_t* __restrict__ rows,
-                                                             const int64_t* __restrict__ src,
-                                                             int64_t n, uint8_t* __restrict__ out,
-                                                             const int64_t* __restrict__ oo,
-                                                             int64_t cap) {
-  copy_rows(rows, [=](int64_t j) { return gl(src)[j]; }, n, out, oo, cap);
 }
 
 }  // namespace

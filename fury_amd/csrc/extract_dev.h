@@ -1,6 +1,8 @@
-// extract_dev.h -- what extract.hip (fury_row_extract) and explode.hip (fury_row_explode), implode.hip and map.hip share: the
-// walk along a path of struct slots, and the compact step that turns per-tile ballots and per-lane
-// (source start, size) pairs into a dense batch.  The designs are described in the two .hip files.
+// extract_dev.h -- what extract.hip (fury_row_extract), explode.hip (fury_row_explode), implode.hip
+// and map.hip share: the walk along a path of struct slots, the compact step that turns per-tile
+// ballots and per-lane (source start, size) pairs into a dense batch, and the two kernels that were the
+// same in two files each: the rank of a validity bitmap's tiles (tile_rank) and the copy from
+// compacted source starts (extract_copy).  The designs are described in the .hip files.
 #pragma once
 
 #include "take_dev.h"
@@ -69,6 +71,28 @@ __device__ __forceinline__ uint64_t tile_word(const uint32_t* bits, int64_t t, i
   const int64_t rem = n - 64 * t;
   return rem < 64 ? w & ((1ull << rem) - 1) : w;
 }
+
+namespace {
+
+// The rank pass of implode.hip and map.hip's join, lane = 64-bit tile t of nt: tr[t] = the popcount
+// of tile_word(bits, t, n), to be scanned.
+__global__ __launch_bounds__(kTakeThreads) void tile_rank(const uint32_t* __restrict__ bits, int64_t n,
+                                                          int64_t nt, int64_t* __restrict__ tr) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
+  if (t < nt) gl(tr)[t] = __popcll(tile_word(bits, t, n));
+}
+
+// The copy pass of extract.hip and explode.hip: n output rows at oo[0..n] (oo[n] = bytes needed);
+// output row j = the bytes at src[j], the compacted source starts.
+__global__ __launch_bounds__(kTakeThreads) void extract_copy(const uint8_t* __restrict__ rows,
+                                                             const int64_t* __restrict__ src,
+                                                             int64_t n, uint8_t* __restrict__ out,
+                                                             const int64_t* __restrict__ oo,
+                                                             int64_t cap) {
+  copy_rows(rows, [=](int64_t j) { return gl(src)[j]; }, n, out, oo, cap);
+}
+
+}  // namespace
 
 // The tile ballot of a locate pass: count, mask and the two validity words of tile t of an output of
 // n positions (validity may be NULL).  Called by the first lane of the wave.

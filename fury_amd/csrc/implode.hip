@@ -26,10 +26,11 @@
 //              (first element, count) for the write pass.  value_offsets is an offsets array, so the
 //              values a row without a failed value takes are ONE run of `values`: its start is kept
 //              too (rsrc).  device_scan makes out_offsets.
-//   write      the structure of copy_rows / select_write (take_dev.h, select.hip): a workgroup owns
-//              kTakeSpan output bytes, finds its rows by the 64-ary search of out_offsets, stages (output
-//              start, first element, count, cs of the first element, payload source) in LDS, and lanes
-//              own 16-byte chunks.  A word finds its row by binary search in LDS and is then GENERATED
+//   write      an instance of write_spans (take_dev.h), the write pass of copy_rows and select_write: a
+//              workgroup owns kTakeSpan output bytes, finds its rows by the 64-ary search of
+//              out_offsets, stages (output start, first element, count, cs of the first element,
+//              payload source) in LDS, and lanes own 16-byte chunks (store_located, which map.hip's
+//              join shares).  A word finds its row by binary search in LDS and is then GENERATED
 //              -- row bitmap, row slot, element count, an array bitmap word (64 bits of the kept ballots
 //              at the row's first element, inverted), an element slot (from cs) -- or COPIED: a payload
 //              byte of a row whose values are one run is at that run's start + its position in the
@@ -53,13 +54,6 @@ namespace {
 constexpr int kTileWaves = kTakeThreads / 64;     // element tiles per workgroup of the elems pass
 constexpr int64_t kMaxElems = (INT32_MAX - 15) / 8;      // BinaryArrayWriter.MAX_ROUNDED_ARRAY_LENGTH
 constexpr int64_t kMaxSize = INT32_MAX - 7;
-
-__global__ __launch_bounds__(kTakeThreads) void implode_rank(const uint32_t* __restrict__ bits,
-                                                             int64_t n, int64_t nt,
-                                                             int64_t* __restrict__ tr) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
-  if (t < nt) gl(tr)[t] = __popcll(tile_word(bits, t, n));
-}
 
 // tr: exclusive scan of the tile popcounts (NULL without a bitmap).  cs[e] = the kept size of element
 // e (to be scanned), src[e] = where its bytes start; km[t] / fm[t]: the ballots "kept" and "present but
@@ -194,149 +188,81 @@ __global__ __launch_bounds__(kTakeThreads) void implode_write(ImplodeArgs a,
                                                               const v2l* __restrict__ info,
                                                               const int64_t* __restrict__ rsrc) {
   __shared__ ImplodeShared sh;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t n = a.nrows;
-  const int64_t* oo = a.out_offsets;
-  uint8_t* out = a.out;
   const int64_t nt = (a.num_elements + 63) >> 6;
-  const int64_t lim = min(gl(oo)[n], a.cap & ~int64_t{7});
-  const uintptr_t ob = reinterpret_cast<uintptr_t>(out);
   const int P = a.prefix;
-  for (int64_t S = static_cast<int64_t>(blockIdx.x) * kTakeSpan; S < lim;
-       S += static_cast<int64_t>(gridDim.x) * kTakeSpan) {
-    const int64_t E = min(S + kTakeSpan, lim);
-    // rows [j0, jl]: the row that holds byte S ... the last row that starts before E
-    const int64_t j0 = last_le(oo, 0, n, S, lane);
-    int64_t jl;
-    {
-      const bool lt = j0 + lane < n && gl(oo)[j0 + lane] < E;
-      const int c = max(__popcll(__ballot(lt)) - 1, 0);
-      jl = c < 63 ? j0 + c : last_le(oo, j0 + 63, n - (j0 + 63), E - 1, lane);
+  auto stage = [&](int64_t r, int k) {
+    const v2l in = gl(info)[r];
+    sh.first[k] = in.x;
+    sh.cnt[k] = in.y;
+    sh.cs0[k] = gl(cs)[in.x];
+    sh.from[k] = gl(rsrc)[r];
+  };
+  // Byte x of staged row f (every row has bytes).  A payload byte: returns true with where in `values`
+  // it is and how many bytes follow it there (to the end of the row's run, or of its value in a row
+  // that skips one); a generated word: returns false with the word.
+  auto locate = [&](int f, int64_t x, uint64_t* word, int64_t* at, int64_t* left) {
+    const int64_t cnt = sh.cnt[f], p0 = sh.first[f];
+    if (x < P) {                      // the one-field row's bitmap word and slot
+      *word = x == 0 ? (cnt < 0 ? 1 : 0)
+                     : (cnt < 0 ? 0 : (16ull << 32) | static_cast<uint64_t>(sh.oo[f + 1] - sh.oo[f] - 16));
+      return false;
     }
-    for (int64_t r0 = j0; r0 <= jl; r0 += kImpRows) {
-      const int kn = static_cast<int>(min<int64_t>(kImpRows, jl + 1 - r0));
-      for (int k = tid; k <= kn; k += kTakeThreads) {
-        sh.oo[k] = gl(oo)[r0 + k];
-        if (k < kn) {
-          const v2l in = gl(info)[r0 + k];
-          sh.first[k] = in.x;
-          sh.cnt[k] = in.y;
-          sh.cs0[k] = gl(cs)[in.x];
-          sh.from[k] = gl(rsrc)[r0 + k];
-        }
+    int64_t y = x - P, e = p0;
+    const int64_t from = sh.from[f];
+    if (!a.wrap) {
+      if (y == 0) {
+        *word = static_cast<uint64_t>(cnt);
+        return false;
       }
-      lds_barrier();
-      auto find = [&](int64_t d) {    // the staged row that holds output byte d (every row has bytes)
-        int lo = 0, hi = kn - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (sh.oo[mid] <= d) lo = mid;
-          else hi = mid - 1;
+      const int64_t bm = ((cnt + 63) >> 6) << 3, H = 8 + bm + 8 * cnt;
+      if (y < 8 + bm) {               // null bits of elements [p0 + i0, p0 + i0 + 64), those below cnt
+        const int64_t i0 = (y - 8) << 3, e0 = p0 + i0;
+        const int64_t t = e0 >> 6;
+        const int sft = static_cast<int>(e0 & 63);
+        uint64_t kept = gl(km)[t] >> sft;
+        if (sft && t + 1 < nt) kept |= gl(km)[t + 1] << (64 - sft);
+        const int64_t c = cnt - i0;
+        *word = ~kept & (c < 64 ? (1ull << c) - 1 : ~0ull);
+        return false;
+      }
+      if (y < H) {
+        const int64_t el = p0 + ((y - 8 - bm) >> 3);
+        *word = 0;
+        if ((gl(km)[el >> 6] >> (el & 63)) & 1) {
+          const int64_t c0 = gl(cs)[el];
+          *word = (static_cast<uint64_t>(H + (c0 - sh.cs0[f])) << 32) |
+                  static_cast<uint64_t>(gl(cs)[el + 1] - c0);
         }
-        return lo;
-      };
-      // Byte x of staged row f.  A payload byte: returns true with where in `values` it is and how
-      // many bytes follow it there (to the end of the row's run, or of its value in a row that skips
-      // one); a generated word: returns false with the word.
-      auto locate = [&](int f, int64_t x, uint64_t* word, int64_t* at, int64_t* left) {
-        const int64_t cnt = sh.cnt[f], p0 = sh.first[f];
-        if (x < P) {                  // the one-field row's bitmap word and slot
-          *word = x == 0 ? (cnt < 0 ? 1 : 0)
-                         : (cnt < 0 ? 0 : (16ull << 32) | static_cast<uint64_t>(sh.oo[f + 1] - sh.oo[f] - 16));
-          return false;
-        }
-        int64_t y = x - P, e = p0;
-        const int64_t from = sh.from[f];
-        if (!a.wrap) {
-          if (y == 0) {
-            *word = static_cast<uint64_t>(cnt);
-            return false;
-          }
-          const int64_t bm = ((cnt + 63) >> 6) << 3, H = 8 + bm + 8 * cnt;
-          if (y < 8 + bm) {           // null bits of elements [p0 + i0, p0 + i0 + 64), those below cnt
-            const int64_t i0 = (y - 8) << 3, e0 = p0 + i0;
-            const int64_t t = e0 >> 6;
-            const int sft = static_cast<int>(e0 & 63);
-            uint64_t kept = gl(km)[t] >> sft;
-            if (sft && t + 1 < nt) kept |= gl(km)[t + 1] << (64 - sft);
-            const int64_t c = cnt - i0;
-            *word = ~kept & (c < 64 ? (1ull << c) - 1 : ~0ull);
-            return false;
-          }
-          if (y < H) {
-            const int64_t el = p0 + ((y - 8 - bm) >> 3);
-            *word = 0;
-            if ((gl(km)[el >> 6] >> (el & 63)) & 1) {
-              const int64_t c0 = gl(cs)[el];
-              *word = (static_cast<uint64_t>(H + (c0 - sh.cs0[f])) << 32) |
-                      static_cast<uint64_t>(gl(cs)[el + 1] - c0);
-            }
-            return false;
-          }
-          y -= H;
-          if (from >= 0) {            // the payload is one run of `values`
-            *left = sh.oo[f + 1] - sh.oo[f] - x;
-            *at = from + y;
-            return true;
-          }
-          // the last element of the row whose clean offset is <= the byte's has bytes there
-          const int64_t p = sh.cs0[f] + y;
-          int64_t hi = p0 + cnt - 1;
-          while (e < hi) {
-            const int64_t mid = (e + hi + 1) >> 1;
-            if (gl(cs)[mid] <= p) e = mid;
-            else hi = mid - 1;
-          }
-          y = p - gl(cs)[e];
-          *left = gl(cs)[e + 1] - p;
-          *at = gl(src)[e] + y;
-        } else {                      // a wrapped value: the row's payload
-          *left = sh.oo[f + 1] - sh.oo[f] - x;
-          *at = from + y;
-        }
+        return false;
+      }
+      y -= H;
+      if (from >= 0) {                // the payload is one run of `values`
+        *left = sh.oo[f + 1] - sh.oo[f] - x;
+        *at = from + y;
         return true;
-      };
-      auto word_at = [&](int64_t d) -> uint64_t {
-        const int f = find(d);
-        uint64_t w;
-        int64_t at, left;
-        if (!locate(f, d - sh.oo[f], &w, &at, &left)) return w;
-        return ld8(a.values + at);
-      };
-      // this round's bytes [a0, b0): 16-byte aligned chunks [A, B), one 8-byte word at either end
-      const int64_t a0 = max(S, sh.oo[0]), b0 = min(E, sh.oo[kn]);
-      int64_t A = a0 + static_cast<int64_t>((16 - ((ob + a0) & 15)) & 15);
-      int64_t B = b0 - static_cast<int64_t>((ob + b0) & 15);
-      if (A > B) A = B = b0;
-      if (tid == 0 && a0 < A) st8(out + a0, word_at(a0));
-      if (tid == 64 && B < b0) st8(out + B, word_at(B));
-      for (int64_t d = A + 16 * tid; d < B; d += 16 * kTakeThreads) {
-        v2q v;
-        const int f = find(d);
-        uint64_t w;
-        int64_t at, left;
-        if (locate(f, d - sh.oo[f], &w, &at, &left)) {
-          const uint8_t* p = a.values + at;
-          if (left >= 16) {
-            if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-              v = ld16(p);
-            } else {
-              v.x = ld8(p);
-              v.y = ld8(p + 8);
-            }
-          } else {                    // the value ends with this word
-            v.x = ld8(p);
-            v.y = word_at(d + 8);
-          }
-        } else {
-          v.x = w;
-          v.y = word_at(d + 8);
-        }
-        st16(out + d, v);
       }
-      lds_barrier();                  // the next round (or span) overwrites the staged rows
+      // the last element of the row whose clean offset is <= the byte's has bytes there
+      const int64_t p = sh.cs0[f] + y;
+      int64_t hi = p0 + cnt - 1;
+      while (e < hi) {
+        const int64_t mid = (e + hi + 1) >> 1;
+        if (gl(cs)[mid] <= p) e = mid;
+        else hi = mid - 1;
+      }
+      y = p - gl(cs)[e];
+      *left = gl(cs)[e + 1] - p;
+      *at = gl(src)[e] + y;
+    } else {                          // a wrapped value: the row's payload
+      *left = sh.oo[f + 1] - sh.oo[f] - x;
+      *at = from + y;
     }
-  }
+    return true;
+  };
+  write_spans<kImpRows>(sh, a.nrows, a.out_offsets, a.cap, stage,
+                        [&](int64_t, int kn, int64_t a0, int64_t b0) {
+                          store_located<int64_t>(a.out, a0, b0, sh.oo, kn, locate,
+                                                 [&](int64_t at) { return a.values + at; });
+                        });
 }
 
 }  // namespace
@@ -363,7 +289,7 @@ int launch_implode(const ImplodeArgs& a, hipStream_t stream) {
   int64_t* tr = a.elem_validity ? tf + nt + 1 : nullptr;
   int64_t* rsrc = tf + 2 * (nt + 1);
   if (tr && nt > 0) {
-    hipLaunchKernelGGL(implode_rank, dim3(blocks_of(nt)), dim3(kTakeThreads), 0, stream,
+    hipLaunchKernelGGL(tile_rank, dim3(blocks_of(nt)), dim3(kTakeThreads), 0, stream,
                        a.elem_validity, E, nt, tr);
     device_scan(tr, nt, tr + nt, sws, stream);
   }

@@ -22,12 +22,13 @@
 //              blockIdx.x the 16 KB span of its bytes, so either side spreads over as many workgroups
 //              as it has spans whatever the other side holds.
 // Join (implode.hip's fused variant with element = row and two runs per row):
-//   rank       lane = 64-row tile: the popcount of its validity word, then device_scan.  Skipped
-//              without a bitmap.
+//   rank       lane = 64-row tile: the popcount of its validity word (tile_rank of extract_dev.h,
+//              implode's kernel), then device_scan.  Skipped without a bitmap.
 //   rows       lane = row, O(1): the value index, both value checks, the two counts, the sizes; per
 //              row (key start, key size | -1) and the value start.  device_scan makes out_offsets.
-//   write      a workgroup owns kTakeSpan output bytes, finds its rows by the 64-ary search of
-//              out_offsets, stages them in LDS, and lanes own 16-byte chunks.  A word is GENERATED
+//   write      write_spans / store_located of take_dev.h, as implode_write: a workgroup owns
+//              kTakeSpan output bytes, finds its rows by the 64-ary search of out_offsets, stages
+//              them in LDS, and lanes own 16-byte chunks.  A word is GENERATED
 //              (row bitmap, row slot, the key-size word, the empty map) or COPIED from the row's key or
 //              value run: one 16-byte non-temporal load when the source aligns, else two 8-byte ones.
 // Nothing loops over a row's bytes or entries: a 70,000-entry map among empty rows is as many copy /
@@ -160,12 +161,6 @@ __global__ __launch_bounds__(kTakeThreads) void map_copy(const uint8_t* __restri
 }
 
 // ---- join ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kTakeThreads) void map_rank(const uint32_t* __restrict__ bits, int64_t n,
-                                                         int64_t nt, int64_t* __restrict__ tr) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
-  if (t < nt) gl(tr)[t] = __popcll(tile_word(bits, t, n));
-}
-
 __device__ __forceinline__ bool value_ok(int64_t s0, int64_t s1, int64_t T) {
   return s0 >= 0 && s0 <= s1 && s1 <= T && !((s0 | s1) & 7) && s1 - s0 >= 8;
 }
@@ -229,114 +224,45 @@ __global__ __launch_bounds__(kTakeThreads) void map_join_write(MapJoinArgs a,
                                                                const v2l* __restrict__ info,
                                                                const int64_t* __restrict__ vsrc) {
   __shared__ MapShared sh;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t n = a.nrows;
-  const int64_t* oo = a.out_offsets;
-  uint8_t* out = a.out;
-  const int64_t lim = min(gl(oo)[n], a.cap & ~int64_t{7});
-  const uintptr_t ob = reinterpret_cast<uintptr_t>(out);
   const int P = a.prefix;
-  for (int64_t S = static_cast<int64_t>(blockIdx.x) * kTakeSpan; S < lim;
-       S += static_cast<int64_t>(gridDim.x) * kTakeSpan) {
-    const int64_t E = min(S + kTakeSpan, lim);
-    // rows [j0, jl]: the row that holds byte S ... the last row that starts before E
-    const int64_t j0 = last_le(oo, 0, n, S, lane);
-    int64_t jl;
-    {
-      const bool lt = j0 + lane < n && gl(oo)[j0 + lane] < E;
-      const int c = max(__popcll(__ballot(lt)) - 1, 0);
-      jl = c < 63 ? j0 + c : last_le(oo, j0 + 63, n - (j0 + 63), E - 1, lane);
+  auto stage = [&](int64_t r, int k) {
+    const v2l in = gl(info)[r];
+    sh.ksrc[k] = in.x;
+    sh.ksz[k] = in.y;
+    sh.vsrc[k] = gl(vsrc)[r];
+  };
+  // Byte x of staged row f (every row has bytes).  A byte of the key or value run: returns true with
+  // its address and how many bytes of the run follow it; a generated word: returns false with the word.
+  auto locate = [&](int f, int64_t x, uint64_t* word, const uint8_t** at, int64_t* left) {
+    const int64_t ksz = sh.ksz[f];
+    if (x < P) {                      // the one-field row's bitmap word and slot
+      *word = x == 0 ? (ksz < 0 ? 1 : 0)
+                     : (ksz < 0 ? 0 : (16ull << 32) | static_cast<uint64_t>(sh.oo[f + 1] - sh.oo[f] - 16));
+      return false;
     }
-    for (int64_t r0 = j0; r0 <= jl; r0 += kMapRows) {
-      const int kn = static_cast<int>(min<int64_t>(kMapRows, jl + 1 - r0));
-      for (int k = tid; k <= kn; k += kTakeThreads) {
-        sh.oo[k] = gl(oo)[r0 + k];
-        if (k < kn) {
-          const v2l in = gl(info)[r0 + k];
-          sh.ksrc[k] = in.x;
-          sh.ksz[k] = in.y;
-          sh.vsrc[k] = gl(vsrc)[r0 + k];
-        }
-      }
-      lds_barrier();
-      auto find = [&](int64_t d) {    // the staged row that holds output byte d (every row has bytes)
-        int lo = 0, hi = kn - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (sh.oo[mid] <= d) lo = mid;
-          else hi = mid - 1;
-        }
-        return lo;
-      };
-      // Byte x of staged row f.  A byte of the key or value run: returns true with its address and how
-      // many bytes of the run follow it; a generated word: returns false with the word.
-      auto locate = [&](int f, int64_t x, uint64_t* word, const uint8_t** at, int64_t* left) {
-        const int64_t ksz = sh.ksz[f];
-        if (x < P) {                  // the one-field row's bitmap word and slot
-          *word = x == 0 ? (ksz < 0 ? 1 : 0)
-                         : (ksz < 0 ? 0 : (16ull << 32) | static_cast<uint64_t>(sh.oo[f + 1] - sh.oo[f] - 16));
-          return false;
-        }
-        const int64_t y = x - P;
-        if (ksz < 0) {                // the empty map: [8][0][0]
-          *word = y == 0 ? 8 : 0;
-          return false;
-        }
-        if (y == 0) {
-          *word = static_cast<uint64_t>(ksz);
-          return false;
-        }
-        if (y < 8 + ksz) {
-          *at = a.keys + sh.ksrc[f] + (y - 8);
-          *left = 8 + ksz - y;
-        } else {
-          *at = a.values + sh.vsrc[f] + (y - 8 - ksz);
-          *left = sh.oo[f + 1] - sh.oo[f] - x;
-        }
-        return true;
-      };
-      auto word_of = [&](int64_t d) -> uint64_t {
-        const int f = find(d);
-        uint64_t w;
-        const uint8_t* p;
-        int64_t left;
-        if (!locate(f, d - sh.oo[f], &w, &p, &left)) return w;
-        return ld8(p);
-      };
-      // this round's bytes [a0, b0): 16-byte aligned chunks [A, B), one 8-byte word at either end
-      const int64_t a0 = max(S, sh.oo[0]), b0 = min(E, sh.oo[kn]);
-      int64_t A = a0 + static_cast<int64_t>((16 - ((ob + a0) & 15)) & 15);
-      int64_t B = b0 - static_cast<int64_t>((ob + b0) & 15);
-      if (A > B) A = B = b0;
-      if (tid == 0 && a0 < A) st8(out + a0, word_of(a0));
-      if (tid == 64 && B < b0) st8(out + B, word_of(B));
-      for (int64_t d = A + 16 * tid; d < B; d += 16 * kTakeThreads) {
-        v2q v;
-        const int f = find(d);
-        uint64_t w;
-        const uint8_t* p;
-        int64_t left;
-        if (locate(f, d - sh.oo[f], &w, &p, &left)) {
-          if (left >= 16) {
-            if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-              v = ld16(p);
-            } else {
-              v.x = ld8(p);
-              v.y = ld8(p + 8);
-            }
-          } else {                    // the run ends with this word
-            v.x = ld8(p);
-            v.y = word_of(d + 8);
-          }
-        } else {
-          v.x = w;
-          v.y = word_of(d + 8);
-        }
-        st16(out + d, v);
-      }
-      lds_barrier();                  // the next round (or span) overwrites the staged rows
+    const int64_t y = x - P;
+    if (ksz < 0) {                    // the empty map: [8][0][0]
+      *word = y == 0 ? 8 : 0;
+      return false;
     }
-  }
+    if (y == 0) {
+      *word = static_cast<uint64_t>(ksz);
+      return false;
+    }
+    if (y < 8 + ksz) {
+      *at = a.keys + sh.ksrc[f] + (y - 8);
+      *left = 8 + ksz - y;
+    } else {
+      *at = a.values + sh.vsrc[f] + (y - 8 - ksz);
+      *left = sh.oo[f + 1] - sh.oo[f] - x;
+    }
+    return true;
+  };
+  write_spans<kMapRows>(sh, a.nrows, a.out_offsets, a.cap, stage,
+                        [&](int64_t, int kn, int64_t a0, int64_t b0) {
+                          store_located<const uint8_t*>(a.out, a0, b0, sh.oo, kn, locate,
+                                                        [](const uint8_t* p) { return p; });
+                        });
 }
 
 }  // namespace
@@ -398,7 +324,7 @@ int launch_map_join(const MapJoinArgs& a, hipStream_t stream) {
   int64_t* vsrc = sws + sw;
   int64_t* tr = a.validity ? vsrc + n : nullptr;
   if (tr) {
-    hipLaunchKernelGGL(map_rank, dim3(blocks_of(nt)), dim3(kTakeThreads), 0, stream, a.validity, n, nt,
+    hipLaunchKernelGGL(tile_rank, dim3(blocks_of(nt)), dim3(kTakeThreads), 0, stream, a.validity, n, nt,
                        tr);
     device_scan(tr, nt, tr + nt, sws, stream);
   }

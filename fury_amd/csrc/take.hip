@@ -15,17 +15,19 @@
 //              and its size at tile base + popcount of the lower mask bits.  Entries at or past the
 //              count are filled by the lane of that position (-1 / size 0), so every entry is
 //              written exactly once.  The count stays on the device: everything after reads it there.
-//   copy       (copy_rows of take_dev.h, which extract.hip instantiates too)
-//              output-parallel and balanced by bytes: a workgroup owns kTakeSpan bytes of the output
-//              (grid-stride over spans), finds the first and last row of its span by a 64-ary search
-//              of out_offsets (one probe per lane, 4 dependent loads for 16 M rows), stages the
-//              (out start, source start) pairs of those rows in LDS -- in rounds of kTakeRows, any
-//              number of 0-byte rows may sit in a span -- and then lanes own 16-byte aligned output
-//              chunks: binary search in LDS for the chunk's row (as unframe_copy), one 16-byte load
-//              when source and destination are congruent mod 16, else two 8-byte loads (the second
-//              one from the next row when the chunk straddles two rows: rows are multiples of 8 bytes
-//              at 8-byte alignment), kTakeInFlight chunks loaded before the first non-temporal
-//              16-byte store.  The unaligned head / tail word of a round goes out as 8 bytes.
+//   copy       (copy_rows of take_dev.h: an instance of write_spans, the one write pass that
+//              extract, explode, select, zip, implode and map instantiate too)
+//              output-parallel and balanced by bytes.  write_spans: a workgroup owns kTakeSpan bytes
+//              of the output (grid-stride over spans), finds the first and last row of its span by a
+//              64-ary search of out_offsets (one probe per lane, 4 dependent loads for 16 M rows) and
+//              stages the rows' output starts and what else its caller keeps per row -- here the
+//              source start -- in LDS, in rounds of kTakeRows: any number of 0-byte rows may sit in a
+//              span.  store_split: lanes own 16-byte aligned output chunks, the unaligned head / tail
+//              word of a round goes out as 8 bytes.  copy_rows' chunk: binary search in LDS for the
+//              chunk's row (staged_row, as unframe_copy), one 16-byte load when source and
+//              destination are congruent mod 16, else two 8-byte loads (the second one from the next
+//              row when the chunk straddles two rows: rows are multiples of 8 bytes at 8-byte
+//              alignment), kTakeInFlight chunks loaded before the first non-temporal 16-byte store.
 //   fixed      rows of is_fixed schemas sit at j * fixed_size: no offsets, no scan, no search; the
 //              chunk's row is its word index / words per row by multiply-high (as update.hip).
 // Bounds: a source row is read only when its index is in [0, nrows) and its extent lies in
@@ -104,16 +106,6 @@ __global__ __launch_bounds__(kTakeThreads) void filter_write(const uint8_t* __re
     if (idx) gl(idx)[r] = -1;
     if (oo) gl(oo)[r] = 0;
   }
-}
-
-// Offsets of fixed-size rows: oo[g] = min(g, count) * fixed_size for g in [0, n].
-__global__ __launch_bounds__(kTakeThreads) void fixed_offsets(int64_t* __restrict__ oo, int64_t n,
-                                                              const int64_t* __restrict__ count,
-                                                              int64_t fixed_size) {
-  const int64_t g = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
-  if (g > n) return;
-  const int64_t cnt = count ? *gl(count) : n;
-  gl(oo)[g] = (g < cnt ? g : cnt) * fixed_size;
 }
 
 // n output rows at oo[0..n] (oo[n] = bytes needed); output row j = source row idx[j].

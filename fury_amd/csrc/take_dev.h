@@ -1,7 +1,11 @@
-// take_dev.h -- the byte-balanced, output-parallel row copy shared by take.hip (fury_row_take /
-// fury_row_filter), extract.hip (fury_row_extract) and explode.hip (fury_row_explode).  Each
-// includes it (the last two through extract_dev.h) and instantiates copy_rows with its own lookup
-// of an output row's source start; the design is described in take.hip.
+// take_dev.h -- the byte-balanced, output-parallel write pass of every operator that makes a row
+// batch, once: write_spans (the span loop, the row search, the staging rounds) and store_split (the
+// 16-byte alignment of a round's stores); the design is described in take.hip.  Its instances:
+//   copy_rows       a row is a run of source bytes: take.hip, extract.hip, explode.hip and map.hip's
+//                   split each give it their lookup of an output row's source start
+//   select_write, zip_write              every 8-byte word is made on its own (store_words)
+//   implode_write, map_join_write        a word is generated or copied from a run (store_located)
+// take.hip includes it directly, the other files through select_dev.h or extract_dev.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,22 +57,104 @@ __device__ __forceinline__ int64_t last_le(const int64_t* oo, int64_t lo, int64_
   return lo;
 }
 
-struct TakeShared {
-  int64_t oo[kTakeRows + 1];          // output start of the staged rows, and the end of the last one
-  int64_t src[kTakeRows];             // source start (0-byte rows: unused)
-};
+// The staged row of a round that holds output byte d: the largest f in [0, kn) with soo[f] <= d, for
+// the kn staged starts soo (LDS) with soo[0] <= d.  A row without bytes is never the answer.
+__device__ __forceinline__ int staged_row(const int64_t* soo, int kn, int64_t d) {
+  int lo = 0, hi = kn - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (soo[mid] <= d) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
 
-// The body of a copy kernel of kTakeThreads threads: n output rows at oo[0..n] (oo[n] = bytes
-// needed); output row j = the oo[j + 1] - oo[j] bytes of `rows` at src_of(j).  src_of is asked only
-// for rows that have bytes.
-template <class SrcOf>
-__device__ __forceinline__ void copy_rows(const uint8_t* __restrict__ rows, SrcOf src_of, int64_t n,
-                                          uint8_t* __restrict__ out,
-                                          const int64_t* __restrict__ oo, int64_t cap) {
-  __shared__ TakeShared sh;
+// Stores output bytes [a, b) (multiples of 8; every thread of the workgroup calls it): chunks(A, B)
+// stores the 16-byte aligned chunks [A, B), and the 8-byte word that an `out` at 8 mod 16 leaves at
+// either end is word(d), stored by thread 0 and thread 64.  Less than one aligned chunk: A = B.
+template <class Word, class Chunks>
+__device__ __forceinline__ void store_split(uint8_t* out, int64_t a, int64_t b, Word word,
+                                            Chunks chunks) {
+  const int tid = threadIdx.x;
+  const uintptr_t ob = reinterpret_cast<uintptr_t>(out);
+  int64_t A = a + static_cast<int64_t>((16 - ((ob + a) & 15)) & 15);
+  int64_t B = b - static_cast<int64_t>((ob + b) & 15);
+  if (A > B) A = B = b;
+  if (tid == 0 && a < A) st8(out + a, word(a));
+  if (tid == 64 && B < b) st8(out + B, word(B));
+  chunks(A, B);
+}
+
+// store_split with the plain chunk loop: a lane makes both words of its chunk with word(d).
+template <class Word>
+__device__ __forceinline__ void store_words(uint8_t* out, int64_t a, int64_t b, Word word) {
+  store_split(out, a, b, word, [&](int64_t A, int64_t B) {
+    for (int64_t d = A + 16 * threadIdx.x; d < B; d += 16 * kTakeThreads) {
+      v2q v;
+      v.x = word(d);
+      v.y = word(d + 8);
+      st16(out + d, v);
+    }
+  });
+}
+
+// store_split for rows whose words are GENERATED or COPIED from a run of source bytes.
+// locate(f, x, &w, &at, &left), byte x of staged row f: true with where the source byte is (an At:
+// addr(at) is its address) and how many bytes of its run follow there, or false with the generated
+// word w.  A chunk inside one run is one 16-byte load when the source aligns, else two 8-byte ones.
+template <class At, class Locate, class Addr>
+__device__ __forceinline__ void store_located(uint8_t* out, int64_t a, int64_t b, const int64_t* soo,
+                                              int kn, Locate locate, Addr addr) {
+  auto word = [&](int64_t d) -> uint64_t {
+    const int f = staged_row(soo, kn, d);
+    uint64_t w;
+    At at;
+    int64_t left;
+    if (!locate(f, d - soo[f], &w, &at, &left)) return w;
+    return ld8(addr(at));
+  };
+  store_split(out, a, b, word, [&](int64_t A, int64_t B) {
+    for (int64_t d = A + 16 * threadIdx.x; d < B; d += 16 * kTakeThreads) {
+      v2q v;
+      const int f = staged_row(soo, kn, d);
+      uint64_t w;
+      At at;
+      int64_t left;
+      if (locate(f, d - soo[f], &w, &at, &left)) {
+        const uint8_t* p = addr(at);
+        if (left >= 16) {
+          if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            v = ld16(p);
+          } else {
+            v.x = ld8(p);
+            v.y = ld8(p + 8);
+          }
+        } else {                      // the run ends with this word
+          v.x = ld8(p);
+          v.y = word(d + 8);
+        }
+      } else {
+        v.x = w;
+        v.y = word(d + 8);
+      }
+      st16(out + d, v);
+    }
+  });
+}
+
+// The output-parallel, byte-balanced write pass of a kernel of kTakeThreads threads: n output rows at
+// oo[0..n] (oo[n] = bytes needed), written below min(oo[n], cap & ~7).  A workgroup owns kTakeSpan
+// output bytes (grid-stride over spans), finds the rows [j0, jl] of its span by the 64-ary search,
+// and stages them in rounds of kRows: sh.oo[0..kn] receives the kn rows' output starts and the end of
+// the last one, stage(r, k) puts whatever else the caller keeps of row r into slot k of sh.  Between
+// the round's two barriers round(r0, kn, a, b) stores the round's bytes [a, b) -- those of rows
+// [r0, r0 + kn) inside the span -- through store_split or one of its two forms above.
+template <int kRows, class Shared, class Stage, class Round>
+__device__ __forceinline__ void write_spans(Shared& sh, int64_t n, const int64_t* __restrict__ oo,
+                                            int64_t cap, Stage stage, Round round) {
+  static_assert(sizeof(sh.oo) == (kRows + 1) * sizeof(int64_t), "sh.oo holds kRows starts and an end");
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t lim = min(gl(oo)[n], cap & ~int64_t{7});
-  const uintptr_t ob = reinterpret_cast<uintptr_t>(out);
   for (int64_t S = static_cast<int64_t>(blockIdx.x) * kTakeSpan; S < lim;
        S += static_cast<int64_t>(gridDim.x) * kTakeSpan) {
     const int64_t E = min(S + kTakeSpan, lim);
@@ -80,68 +166,90 @@ __device__ __forceinline__ void copy_rows(const uint8_t* __restrict__ rows, SrcO
       const int c = max(__popcll(__ballot(lt)) - 1, 0);
       jl = c < 63 ? j0 + c : last_le(oo, j0 + 63, n - (j0 + 63), E - 1, lane);
     }
-    for (int64_t r0 = j0; r0 <= jl; r0 += kTakeRows) {
-      const int kn = static_cast<int>(min<int64_t>(kTakeRows, jl + 1 - r0));
+    for (int64_t r0 = j0; r0 <= jl; r0 += kRows) {
+      const int kn = static_cast<int>(min<int64_t>(kRows, jl + 1 - r0));
       for (int k = tid; k <= kn; k += kTakeThreads) {
-        const int64_t o = gl(oo)[r0 + k];
-        sh.oo[k] = o;
-        if (k < kn) sh.src[k] = gl(oo)[r0 + k + 1] > o ? src_of(r0 + k) : 0;
+        sh.oo[k] = gl(oo)[r0 + k];
+        if (k < kn) stage(r0 + k, k);
       }
       lds_barrier();
-      auto find = [&](int64_t d) {    // the staged row that holds output byte d (its size is > 0)
-        int lo = 0, hi = kn - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (sh.oo[mid] <= d) lo = mid;
-          else hi = mid - 1;
-        }
-        return lo;
-      };
-      auto word_at = [&](int64_t d) {
-        const int f = find(d);
-        return ld8(rows + sh.src[f] + (d - sh.oo[f]));
-      };
-      // this round's bytes [a, b): 16-byte aligned chunks [A, B), one 8-byte word at either end
-      const int64_t a = max(S, sh.oo[0]), b = min(E, sh.oo[kn]);
-      int64_t A = a + static_cast<int64_t>((16 - ((ob + a) & 15)) & 15);
-      int64_t B = b - static_cast<int64_t>((ob + b) & 15);
-      if (A > B) A = B = b;
-      if (tid == 0 && a < A) st8(out + a, word_at(a));
-      if (tid == 64 && B < b) st8(out + B, word_at(B));
-      for (int64_t d0 = A; d0 < B; d0 += kTakeStep) {
-        v2q v[kTakeInFlight];
-#pragma unroll
-        for (int u = 0; u < kTakeInFlight; u++) {
-          const int64_t d = d0 + 16 * (tid + u * kTakeThreads);
-          v[u] = v2q{0, 0};
-          if (d < B) {
-            const int f = find(d);
-            const uint8_t* p = rows + sh.src[f] + (d - sh.oo[f]);
-            if (sh.oo[f + 1] - d >= 16) {
-              if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-                v[u] = ld16(p);
-              } else {
-                v[u].x = ld8(p);
-                v[u].y = ld8(p + 8);
-              }
-            } else {                  // the chunk's second word starts the next row that has bytes
-              int f2 = f + 1;
-              while (sh.oo[f2 + 1] <= d + 8) f2++;
-              v[u].x = ld8(p);
-              v[u].y = ld8(rows + sh.src[f2]);
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kTakeInFlight; u++) {
-          const int64_t d = d0 + 16 * (tid + u * kTakeThreads);
-          if (d < B) st16(out + d, v[u]);
-        }
-      }
+      round(r0, kn, max(S, sh.oo[0]), min(E, sh.oo[kn]));
       lds_barrier();                  // the next round (or span) overwrites the staged rows
     }
   }
 }
+
+struct TakeShared {
+  int64_t oo[kTakeRows + 1];          // output start of the staged rows, and the end of the last one
+  int64_t src[kTakeRows];             // source start (0-byte rows: unused)
+};
+
+// The body of a copy kernel of kTakeThreads threads: n output rows at oo[0..n] (oo[n] = bytes
+// needed); output row j = the oo[j + 1] - oo[j] bytes of `rows` at src_of(j).  src_of is asked only
+// for rows that have bytes.  write_spans with kTakeInFlight chunks per lane loaded before the first
+// store.
+template <class SrcOf>
+__device__ __forceinline__ void copy_rows(const uint8_t* __restrict__ rows, SrcOf src_of, int64_t n,
+                                          uint8_t* __restrict__ out,
+                                          const int64_t* __restrict__ oo, int64_t cap) {
+  __shared__ TakeShared sh;
+  write_spans<kTakeRows>(
+      sh, n, oo, cap,
+      [&](int64_t r, int k) { sh.src[k] = gl(oo)[r + 1] > gl(oo)[r] ? src_of(r) : 0; },
+      [&](int64_t, int kn, int64_t a, int64_t b) {
+        const int tid = threadIdx.x;
+        auto word_at = [&](int64_t d) {
+          const int f = staged_row(sh.oo, kn, d);
+          return ld8(rows + sh.src[f] + (d - sh.oo[f]));
+        };
+        store_split(out, a, b, word_at, [&](int64_t A, int64_t B) {
+          for (int64_t d0 = A; d0 < B; d0 += kTakeStep) {
+            v2q v[kTakeInFlight];
+#pragma unroll
+            for (int u = 0; u < kTakeInFlight; u++) {
+              const int64_t d = d0 + 16 * (tid + u * kTakeThreads);
+              v[u] = v2q{0, 0};
+              if (d < B) {
+                const int f = staged_row(sh.oo, kn, d);
+                const uint8_t* p = rows + sh.src[f] + (d - sh.oo[f]);
+                if (sh.oo[f + 1] - d >= 16) {
+                  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+                    v[u] = ld16(p);
+                  } else {
+                    v[u].x = ld8(p);
+                    v[u].y = ld8(p + 8);
+                  }
+                } else {              // the chunk's second word starts the next row that has bytes
+                  int f2 = f + 1;
+                  while (sh.oo[f2 + 1] <= d + 8) f2++;
+                  v[u].x = ld8(p);
+                  v[u].y = ld8(rows + sh.src[f2]);
+                }
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < kTakeInFlight; u++) {
+              const int64_t d = d0 + 16 * (tid + u * kTakeThreads);
+              if (d < B) st16(out + d, v[u]);
+            }
+          }
+        });
+      });
+}
+
+namespace {
+
+// Offsets of fixed-size rows: oo[g] = min(g, count) * fixed_size for g in [0, n] (count NULL: n).
+__global__ __launch_bounds__(kTakeThreads) void fixed_offsets(int64_t* __restrict__ oo, int64_t n,
+                                                              const int64_t* __restrict__ count,
+                                                              int64_t fixed_size) {
+  const int64_t g = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
+  if (g > n) return;
+  const int64_t cnt = count ? *gl(count) : n;
+  gl(oo)[g] = (g < cnt ? g : cnt) * fixed_size;
+}
+
+}  // namespace
 
 inline unsigned blocks_of(int64_t n) {
   return static_cast<unsigned>((n + kTakeThreads - 1) / kTakeThreads);

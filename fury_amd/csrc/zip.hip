@@ -20,7 +20,8 @@
 //              (a failed source row or value is already a set bit there), the start W of every
 //              variable-length pick, and the row size.
 //   scan       device_scan of the sizes in out_offsets.
-//   write      select_write with the staged rows' starts kept per source: a workgroup owns kTakeSpan
+//   write      select_write with the staged rows' starts kept per source, the same instance of
+//              write_spans / store_words (take_dev.h) with its own LDS struct: a workgroup owns kTakeSpan
 //              output bytes, kZipRows rows are staged per round (20 KB of LDS with the four source
 //              starts, 30 KB with the table: five workgroups a CU), each 8-byte word is made from its
 //              segment; a payload word finds its value in the row's W list, then that value's source.
@@ -39,28 +40,6 @@ namespace {
 constexpr int kZipLdsWords = 2560;                // 10 KB: 512 fixed-width picks
 constexpr int kZipCoopFields = 16;                // as kSelCoopFields (select.hip)
 constexpr int kZipRows = 512;                     // rows staged in LDS per round of the write pass
-
-using CI32 = __attribute__((address_space(4))) const int32_t;
-__device__ __forceinline__ CI32* table_of(const ZipArgs& a) {
-  return a.tab ? (CI32*)(a.tab) : (CI32*)(a.tabi);
-}
-
-// The table for per-lane lookups: staged in LDS when it fits.  Every thread of the workgroup calls it.
-struct ZipTable {
-  const int32_t* lds;
-  CI32* mem;
-  __device__ __forceinline__ int32_t operator[](int i) const { return lds ? lds[i] : mem[i]; }
-};
-__device__ __forceinline__ ZipTable stage_table(const ZipArgs& a, int32_t* lds) {
-  ZipTable t{nullptr, table_of(a)};
-  const int nw = 5 * a.nsel + a.nvar;
-  if (nw <= kZipLdsWords) {
-    for (int i = threadIdx.x; i < nw; i += kTakeThreads) lds[i] = t.mem[i];
-    lds_barrier();
-    t.lds = lds;
-  }
-  return t;
-}
 
 // One of four values by source index: selects, never an indexed register array.  Used where the index
 // is wave-uniform (the measure pass) and for the row starts, which live in registers.
@@ -107,18 +86,6 @@ __device__ __forceinline__ void stage_sources(const ZipArgs& a, const ZipTotals&
   lds_barrier();
 }
 
-// Row r of one source: its start, and whether its header may be read ("Decode bounds": 8-byte aligned,
-// [B, B + fixed_size) inside [0, total), the row's own extent no shorter than fixed_size).
-__device__ __forceinline__ bool source_row(const ZipSource& z, int64_t r, int64_t total, int64_t* B) {
-  if (!z.row_offsets) {
-    *B = r * z.fixed_size;
-    return true;
-  }
-  const int64_t b = gl(z.row_offsets)[r];
-  *B = b;
-  return !(b & 7) && span_ok(b, z.fixed_size, total) && gl(z.row_offsets)[r + 1] - b >= z.fixed_size;
-}
-
 // Row r of every source that is used: the starts, and bit s of `ok` when the row of s may be read.
 struct ZipRow {
   int64_t b0, b1, b2, b3;
@@ -134,17 +101,11 @@ __device__ __forceinline__ ZipRow row_of(const ZipArgs& a, int64_t r, const ZipT
   return w;
 }
 
-__global__ __launch_bounds__(kTakeThreads) void zip_fixed_offsets(int64_t* __restrict__ oo, int64_t n,
-                                                                  int64_t fixed_size) {
-  const int64_t g = static_cast<int64_t>(blockIdx.x) * kTakeThreads + threadIdx.x;
-  if (g <= n) gl(oo)[g] = g * fixed_size;
-}
-
 // Output rows of Wn 8-byte words at r * Wn; magic = 2^64 / Wn rounded up (exact for the word counts
 // launch_zip admits).
 __global__ __launch_bounds__(kTakeThreads) void zip_fixed(ZipArgs a, uint64_t Wn, uint64_t magic) {
   __shared__ int32_t tl[kZipLdsWords];
-  const ZipTable T = stage_table(a, tl);
+  const StagedTable T = stage_table(table_of(a), 5 * a.nsel + a.nvar, tl, kZipLdsWords);
   const int64_t n = a.nrows;
   const ZipTotals tot = totals_of(a);
   __shared__ ZipLds L;
@@ -307,104 +268,63 @@ __global__ __launch_bounds__(kTakeThreads) void zip_write(ZipArgs a, const uint6
                                                           const int32_t* __restrict__ wW) {
   __shared__ ZipShared sh;
   __shared__ int32_t tl[kZipLdsWords];
-  const ZipTable T = stage_table(a, tl);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t n = a.nrows;
-  const int64_t* oo = a.out_offsets;
-  uint8_t* out = a.out;
+  const StagedTable T = stage_table(table_of(a), 5 * a.nsel + a.nvar, tl, kZipLdsWords);
   const ZipTotals tot = totals_of(a);
   __shared__ ZipLds L;
   stage_sources(a, tot, &L);
-  const int64_t lim = min(gl(oo)[n], a.cap & ~int64_t{7});
-  const uintptr_t ob = reinterpret_cast<uintptr_t>(out);
   const int nbw = a.out_bitmap_bytes >> 3;
-  for (int64_t S = static_cast<int64_t>(blockIdx.x) * kTakeSpan; S < lim;
-       S += static_cast<int64_t>(gridDim.x) * kTakeSpan) {
-    const int64_t E = min(S + kTakeSpan, lim);
-    // rows [j0, jl]: the row that holds byte S ... the last row that starts before E
-    const int64_t j0 = last_le(oo, 0, n, S, lane);
-    int64_t jl;
-    {
-      const bool lt = j0 + lane < n && gl(oo)[j0 + lane] < E;
-      const int c = max(__popcll(__ballot(lt)) - 1, 0);
-      jl = c < 63 ? j0 + c : last_le(oo, j0 + 63, n - (j0 + 63), E - 1, lane);
-    }
-    for (int64_t r0 = j0; r0 <= jl; r0 += kZipRows) {
-      const int kn = static_cast<int>(min<int64_t>(kZipRows, jl + 1 - r0));
-      for (int k = tid; k <= kn; k += kTakeThreads) {
-        sh.oo[k] = gl(oo)[r0 + k];
-        if (k < kn) {
+  auto stage = [&](int64_t r, int k) {
 #pragma unroll
-          for (int s = 0; s < kZipMaxSources; s++) {
-            if (!((a.used >> s) & 1)) continue;
-            const ZipSource& z = a.src[s];
-            sh.src[s][k] = z.row_offsets ? gl(z.row_offsets)[r0 + k] : (r0 + k) * z.fixed_size;
-          }
-        }
-      }
-      lds_barrier();
-      auto word_at = [&](int64_t d) -> uint64_t {
-        int lo = 0, hi = kn - 1;      // the staged row that holds output byte d (every row has bytes)
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (sh.oo[mid] <= d) lo = mid;
-          else hi = mid - 1;
-        }
-        const int64_t r = r0 + lo;
-        const int x = static_cast<int>(d - sh.oo[lo]);
-        if (x < a.out_bitmap_bytes) return gl(wbm)[r * nbw + (x >> 3)];
-        if (x < a.out_fixed_size) {
-          const int j = (x - a.out_bitmap_bytes) >> 3;
-          if ((gl(wbm)[r * nbw + (j >> 6)] >> (j & 63)) & 1) return 0;
-          const int32_t width = T[5 * j + 1];
-          const int s = T[5 * j + 4];
-          const ZipSource z = L.z[s];
-          const uint64_t sl = word(z.rows + sh.src[s][lo] + z.bitmap_bytes + 8 * T[5 * j]);
-          if (width != kSelVar) return fixed_slot(sl, width);
-          const uint64_t W = static_cast<uint32_t>(gl(wW)[r * a.nvar + T[5 * j + 3]]);
-          return (W << 32) | static_cast<uint32_t>(sl);
-        }
-        // payload: the last variable-length pick that starts at or before x has bytes there
-        const int32_t* Wr = wW + r * a.nvar;
-        int vl = 0, vh = a.nvar - 1;
-        while (vl < vh) {
-          const int mid = (vl + vh + 1) >> 1;
-          if (gl(Wr)[mid] <= x) vl = mid;
-          else vh = mid - 1;
-        }
-        const int j = T[5 * a.nsel + vl];
+    for (int s = 0; s < kZipMaxSources; s++) {
+      if (!((a.used >> s) & 1)) continue;
+      const ZipSource& z = a.src[s];
+      sh.src[s][k] = z.row_offsets ? gl(z.row_offsets)[r] : r * z.fixed_size;
+    }
+  };
+  auto round = [&](int64_t r0, int kn, int64_t a0, int64_t b0) {
+    store_words(a.out, a0, b0, [&](int64_t d) -> uint64_t {
+      const int lo = staged_row(sh.oo, kn, d);      // every row has bytes
+      const int64_t r = r0 + lo;
+      const int x = static_cast<int>(d - sh.oo[lo]);
+      if (x < a.out_bitmap_bytes) return gl(wbm)[r * nbw + (x >> 3)];
+      if (x < a.out_fixed_size) {
+        const int j = (x - a.out_bitmap_bytes) >> 3;
+        if ((gl(wbm)[r * nbw + (j >> 6)] >> (j & 63)) & 1) return 0;
+        const int32_t width = T[5 * j + 1];
         const int s = T[5 * j + 4];
         const ZipSource z = L.z[s];
-        const int64_t B = sh.src[s][lo];
-        const uint64_t sl = word(z.rows + B + z.bitmap_bytes + 8 * T[5 * j]);
-        const int64_t pos = x - gl(Wr)[vl];
-        const int64_t left = static_cast<int32_t>(sl) - pos;          // >= 1 bytes of the value
-        const int64_t p = B + static_cast<int32_t>(sl >> 32) + pos;
-        if (left >= 8) return ld8(z.rows + p);
-        uint64_t v = 0;
-        if (p + 8 <= L.tot[s]) {
-          v = ld8(z.rows + p) & ((1ull << (8 * left)) - 1);
-        } else {                      // the value ends its batch: no byte past it is read
-          for (int i = 0; i < left; i++) v |= static_cast<uint64_t>(gl(z.rows)[p + i]) << (8 * i);
-        }
-        return v;
-      };
-      // this round's bytes [a0, b0): 16-byte aligned chunks [A, B), one 8-byte word at either end
-      const int64_t a0 = max(S, sh.oo[0]), b0 = min(E, sh.oo[kn]);
-      int64_t A = a0 + static_cast<int64_t>((16 - ((ob + a0) & 15)) & 15);
-      int64_t B = b0 - static_cast<int64_t>((ob + b0) & 15);
-      if (A > B) A = B = b0;
-      if (tid == 0 && a0 < A) st8(out + a0, word_at(a0));
-      if (tid == 64 && B < b0) st8(out + B, word_at(B));
-      for (int64_t d = A + 16 * tid; d < B; d += 16 * kTakeThreads) {
-        v2q v;
-        v.x = word_at(d);
-        v.y = word_at(d + 8);
-        st16(out + d, v);
+        const uint64_t sl = word(z.rows + sh.src[s][lo] + z.bitmap_bytes + 8 * T[5 * j]);
+        if (width != kSelVar) return fixed_slot(sl, width);
+        const uint64_t W = static_cast<uint32_t>(gl(wW)[r * a.nvar + T[5 * j + 3]]);
+        return (W << 32) | static_cast<uint32_t>(sl);
       }
-      lds_barrier();                  // the next round (or span) overwrites the staged rows
-    }
-  }
+      // payload: the last variable-length pick that starts at or before x has bytes there
+      const int32_t* Wr = wW + r * a.nvar;
+      int vl = 0, vh = a.nvar - 1;
+      while (vl < vh) {
+        const int mid = (vl + vh + 1) >> 1;
+        if (gl(Wr)[mid] <= x) vl = mid;
+        else vh = mid - 1;
+      }
+      const int j = T[5 * a.nsel + vl];
+      const int s = T[5 * j + 4];
+      const ZipSource z = L.z[s];
+      const int64_t B = sh.src[s][lo];
+      const uint64_t sl = word(z.rows + B + z.bitmap_bytes + 8 * T[5 * j]);
+      const int64_t pos = x - gl(Wr)[vl];
+      const int64_t left = static_cast<int32_t>(sl) - pos;          // >= 1 bytes of the value
+      const int64_t p = B + static_cast<int32_t>(sl >> 32) + pos;
+      if (left >= 8) return ld8(z.rows + p);
+      uint64_t v = 0;
+      if (p + 8 <= L.tot[s]) {
+        v = ld8(z.rows + p) & ((1ull << (8 * left)) - 1);
+      } else {                        // the value ends its batch: no byte past it is read
+        for (int i = 0; i < left; i++) v |= static_cast<uint64_t>(gl(z.rows)[p + i]) << (8 * i);
+      }
+      return v;
+    });
+  };
+  write_spans<kZipRows>(sh, a.nrows, a.out_offsets, a.cap, stage, round);
 }
 
 }  // namespace
@@ -412,21 +332,14 @@ __global__ __launch_bounds__(kTakeThreads) void zip_write(ZipArgs a, const uint6
 int launch_zip(const ZipArgs& args, const int32_t* table, int nwords, hipStream_t stream) {
   ZipArgs a = args;
   const int64_t n = a.nrows;
-  // blocks_of() in 31 bits, and the fixed kernel's multiply-high exact
-  if (n >= (int64_t{1} << 38) || n > (int64_t{1} << 52) / a.out_fixed_size)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
   DeviceTable dt;
-  if (nwords <= kZipArgWords) {
-    std::copy(table, table + nwords, a.tabi);
-  } else {
-    const int st = upload_table(table, static_cast<size_t>(nwords) * 4, stream, &dt);
-    if (st) return st;
-    a.tab = static_cast<const int32_t*>(dt.dev);
-  }
+  int st = place_table(&a, table, nwords, stream, &dt);
+  if (st) return st;
   if (a.nvar == 0) {                  // fixed-width picks: row r at r * out_fixed_size
     if (a.out_offsets)
-      hipLaunchKernelGGL(zip_fixed_offsets, dim3(blocks_of(n + 1)), dim3(kTakeThreads), 0, stream,
-                         a.out_offsets, n, static_cast<int64_t>(a.out_fixed_size));
+      hipLaunchKernelGGL(fixed_offsets, dim3(blocks_of(n + 1)), dim3(kTakeThreads), 0, stream,
+                         a.out_offsets, n, static_cast<const int64_t*>(nullptr),
+                         static_cast<int64_t>(a.out_fixed_size));
     if (a.out && n > 0) {
       const uint64_t Wn = static_cast<uint64_t>(a.out_fixed_size) / 8;
       const int64_t chunks = (n * static_cast<int64_t>(Wn) + 1) / 2;
@@ -437,19 +350,15 @@ int launch_zip(const ZipArgs& args, const int32_t* table, int nwords, hipStream_
     return check_hip(hipGetLastError(), "zip launch");
   }
   if (n == 0) return check_hip(hipMemsetAsync(a.out_offsets, 0, 8, stream), "memset");
-  const int64_t nbw = a.out_bitmap_bytes / 8;
-  const int64_t sw = scan_workspace(n);
-  int64_t* ws = nullptr;              // [scan scratch][bitmap words x n nbw][value starts x n nvar (int32)]
-  int st = dev_alloc((sw + n * nbw + (n * a.nvar + 1) / 2) * 8, stream, reinterpret_cast<void**>(&ws));
+  SelectWorkspace w;
+  st = alloc_workspace(a, stream, &w);
   if (st) return st;
-  uint64_t* wbm = reinterpret_cast<uint64_t*>(ws + sw);
-  int32_t* wW = reinterpret_cast<int32_t*>(ws + sw + n * nbw);
-  hipLaunchKernelGGL(zip_measure, dim3(blocks_of(n)), dim3(kTakeThreads), 0, stream, a, wbm, wW);
-  device_scan(a.out_offsets, n, a.out_offsets + n, ws, stream);
+  hipLaunchKernelGGL(zip_measure, dim3(blocks_of(n)), dim3(kTakeThreads), 0, stream, a, w.wbm, w.wW);
+  device_scan(a.out_offsets, n, a.out_offsets + n, w.ws, stream);
   if (a.out && a.cap >= 8)
-    hipLaunchKernelGGL(zip_write, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a, wbm, wW);
+    hipLaunchKernelGGL(zip_write, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a, w.wbm, w.wW);
   st = check_hip(hipGetLastError(), "zip launch");
-  dev_free(ws, stream);
+  dev_free(w.ws, stream);
   return st;
 }
 

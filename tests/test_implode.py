@@ -130,7 +130,7 @@ class Case:
         assert_same(ooffs.cpu().numpy(), np.concatenate([w.offs, [-7]]), f"{what}: out_offsets")
         want = np.full(t.numel(), FILL, np.uint8)
         if not measure:
-            k = min(cap, len(w.data))
+            k = min(cap & ~7, len(w.data))         # a capacity off a multiple of 8 is rounded down
             want[at:at + k] = w.data[:k]
         assert_same(t.cpu().numpy(), want, f"{what}: output buffer")
         self.status(what, stream)
@@ -334,6 +334,29 @@ def test_alignment(dev, n):
         for src_shift, out_shift in ((0, 8), (8, 0), (8, 8)):
             case.run(f"{name} n={n} shifts {src_shift}/{out_shift}", src_shift=src_shift,
                      out_shift=out_shift)
+
+
+def test_write_pass_rounds_and_end_words(dev):
+    """tests.test_select.test_write_pass_rounds_and_end_words for implode_write (implode and wrap), which
+    stages 512 rows a round: one present row of 24 bytes -- an empty list -- ahead of 2049 null rows of
+    16, so the rows start at 8 mod 16, the second 16 KB span is three rounds and the 32,808 bytes are 8
+    mod 16; capacities inside a row, on and off a multiple of 8.  (A list across several spans among
+    short rows: test_one_long_list_among_empty_rows.)"""
+    src = source(dev, "flat", 257)
+    n = 2050
+    first = np.zeros((n + 7) // 8, np.uint8)
+    first[0] = 1
+    empty_list = np.zeros(8, np.uint8)                         # [int64 numElements = 0]
+    cases = {"implode": Case(targets(src, ("items",), "elements")[0], empty_list[:0], [0],
+                             np.zeros(n + 1, np.int64), n, first, None, 0),
+             "wrap": Case(extracted_case(src, ("items",)).enc, empty_list, [0, 8], None, n, None, first, n)}
+    for name, case in cases.items():
+        total = len(case.want.data)
+        assert list(np.diff(case.want.offs)) == [24] + [16] * 2049 and total % 16 == 8
+        for out_shift in (0, 8):
+            for cap in (None, total - 24, total - 20):
+                w = case.run(f"{name}: shift {out_shift} capacity {cap}", cap=cap, out_shift=out_shift)
+                assert not w.bad
 
 
 def test_on_a_side_stream_and_bound_twice(dev):

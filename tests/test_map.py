@@ -216,7 +216,7 @@ class JoinCase:
         assert_same(ooffs.cpu().numpy(), np.concatenate([w.offs, [-7]]), f"{what}: out_offsets")
         want = np.full(t.numel(), FILL, np.uint8)
         if not measure:
-            k = min(cap, len(w.data))
+            k = min(cap & ~7, len(w.data))         # a capacity off a multiple of 8 is rounded down
             want[at:at + k] = w.data[:k]
         assert_same(t.cpu().numpy(), want, f"{what}: output buffer")
         check_status(enc, w.bad, w.bad_counts, what, stream)
@@ -404,6 +404,26 @@ def test_alignment(dev, n):
             joined_case(src, path).run(f"{what}: join", src_shift=src_shift, out_shift=out_shift)
     coll = map_source(dev, "coll", n)
     joined_case(coll, None, rows_form=False).run(f"collection n={n}: join", src_shift=8)
+
+
+def test_write_pass_rounds_and_end_words(dev):
+    """tests.test_select.test_write_pass_rounds_and_end_words for map_join_write, which stages 512 rows a
+    round: one present row of 40 bytes -- a map without entries -- ahead of 2049 null rows of 16, so the
+    rows start at 8 mod 16, a 16 KB span is three rounds and the 32,824 bytes are 8 mod 16;
+    capacities inside a row, on and off a multiple of 8.  (A map across several spans among short rows:
+    test_one_long_map_among_empty_rows.)"""
+    enc = targets(map_source(dev, "flat", 257), ("m",))[0]
+    n = 2050
+    first = np.zeros((n + 7) // 8, np.uint8)
+    first[0] = 1
+    no_entries = np.zeros(8, np.uint8)                         # [int64 numElements = 0]
+    case = JoinCase(enc, no_entries, [0, 8], no_entries, [0, 8], first, n)
+    total = len(case.want.data)
+    assert list(np.diff(case.want.offs)) == [40] + [16] * 2049 and total % 16 == 8
+    for out_shift in (0, 8):
+        for cap in (None, total - 24, total - 20):
+            w = case.run(f"shift {out_shift} capacity {cap}", cap=cap, out_shift=out_shift)
+            assert not w.bad
 
 
 def test_on_a_side_stream_and_bound_twice(dev):

@@ -96,6 +96,9 @@ def source(dev, name, n) -> _Src:
         elif name == "full":
             fields = SCHEMAS["foo"]
             host = beans_to_columns(fields, _full_beans(n))
+        elif name == "nulls":                         # one 8-byte value, then nulls: 24- and 16-byte rows
+            fields = [T.field("s", T.STRING)]
+            host = beans_to_columns(fields, [{"s": None if i else "12345678"} for i in range(n)])
         else:
             fields = SCHEMAS[name]
             host = host_columns(name, n)
@@ -154,7 +157,7 @@ def check_select(src, select, what, cap=None, src_shift=0, out_shift=0, measure=
                 else np.full(n + 2, -7, np.int64), f"{what}: out_offsets")
     want = np.full(t.numel(), FILL, np.uint8)
     if not measure:
-        k = min(cap, len(w.data))
+        k = min(cap & ~7, len(w.data))             # a capacity off a multiple of 8 is rounded down
         want[at:at + k] = w.data[:k]
     assert_same(t.cpu().numpy(), want, f"{what}: output buffer")
     return w
@@ -457,6 +460,23 @@ def test_select_alignment(dev, n):
             check_select(src, sel, f"{name} n={n} shifts {src_shift}/{out_shift}",
                          src_shift=src_shift, out_shift=out_shift)
         src.enc.device_status()
+
+
+def test_write_pass_rounds_and_end_words(dev):
+    """The index arithmetic of write_spans / store_split (take_dev.h) in select_write, at its edges that
+    the tests above leave out (a value across several spans: test_value_sizes).  One 24-byte row ahead of
+    2049 null rows of 16 bytes: every later row starts at 8 mod 16, so the second 16 KB span touches 1025
+    rows -- a second staging round of one row -- and the 32,808 bytes are 8 mod 16: into a buffer at 8
+    mod 16 the head and the tail word are single 8-byte stores.  A capacity inside a row, on and off a
+    multiple of 8: bytes below cap & ~7 are the full result's, the fill stays from there on, the offsets
+    are complete (check_select compares the whole guarded buffer)."""
+    src = source(dev, "nulls", 2050)
+    total = len(src.want(["s"]).data)
+    assert total == 24 + 2049 * 16 and total % 16 == 8
+    for out_shift in (0, 8):
+        for cap in (None, total - 24, total - 20):
+            check_select(src, ["s"], f"nulls shift {out_shift} capacity {cap}", cap=cap, out_shift=out_shift)
+    src.enc.device_status()
 
 
 def test_select_on_a_side_stream_and_bound_twice(dev):

@@ -117,7 +117,7 @@ def _out_buffer(dev, cap, shift):
 
 def _filled(size, at, data, cap):
     want = np.full(size, FILL, np.uint8)
-    k = min(cap, len(data))
+    k = min(cap & ~7, len(data))                   # a capacity off a multiple of 8 is rounded down
     want[at:at + k] = data[:k]
     return want
 
@@ -213,6 +213,32 @@ def test_take_long_row(dev):
         for src_shift, out_shift in ((0, 0), (8, 0), (0, 8), (8, 8)):
             check_take(src, sel, f"long row, {what}, shifts {src_shift}/{out_shift}",
                        src_shift=src_shift, out_shift=out_shift)
+    src.enc.device_status()
+
+
+def test_copy_rounds_and_end_words(dev):
+    """The index arithmetic of write_spans / store_split (take_dev.h) in copy_rows at its edges.  A row
+    whose index is bad has no bytes: one 24-byte row, 2100 such rows, 1100 rows of 16 bytes, the
+    200,016-byte row and three more short ones.  The first 16 KB span then touches more than 3,000 rows
+    in four staging rounds, the second of which has no byte at all -- at 8 mod 16 in an aligned buffer,
+    the round without a single aligned chunk -- the long row crosses a dozen spans whose first and last
+    hold other rows too, and the total is 8 mod 16: into a buffer at 8 mod 16 the head and the tail word
+    are single 8-byte stores.  Capacities inside a row, on and off a multiple of 8: bytes below cap & ~7
+    are the full result's, the fill stays from there on, the offsets are complete."""
+    from fury_amd.encoder import IndexOutOfBoundsException
+    src = _string_source(dev)
+    sel = np.array([3] + [-1] * 2100 + [0] * 1100 + [9, 0, 0, 0], np.int64)
+    data, eoffs, bad = expect(src.rows, src.offs, src.n, sel)
+    total = len(data)
+    assert eoffs[1] == 24 and eoffs[2101] == 24 and total == 24 + 1103 * 16 + 200_016 and total % 16 == 8
+    src.enc.device_status()
+    for out_shift in (0, 8):
+        for cap in (None, total - 24, total - 20, 16384 + 24):
+            got = check_take(src, sel, f"zero-byte rows, shift {out_shift} capacity {cap}", cap=cap,
+                             out_shift=out_shift)
+            assert got == list(range(1, 2101))
+            with pytest.raises(IndexOutOfBoundsException):
+                src.enc.device_status()
     src.enc.device_status()
 
 

@@ -100,7 +100,7 @@ def check_zip(srcs, picks, what, cap=None, out_shift=0, measure=False, stream=No
                 else np.full(n + 2, -7, np.int64), f"{what}: out_offsets")
     expect = np.full(t.numel(), FILL, np.uint8)
     if not measure:
-        k = min(cap, len(w.data))
+        k = min(cap & ~7, len(w.data))             # a capacity off a multiple of 8 is rounded down
         expect[at:at + k] = w.data[:k]
     assert_same(t.cpu().numpy(), expect, f"{what}: output buffer")
     return w
@@ -214,6 +214,22 @@ def test_capacities_and_the_measure_form(dev):
             check_zip(srcs, picks, f"capacity {cap} of {total}", cap=cap, out_shift=out_shift, want=w)
     check_zip(srcs, picks, "measure form", measure=True, want=w)
     srcs[0].enc.device_status()
+
+
+def test_write_pass_rounds_and_end_words(dev):
+    """tests.test_select.test_write_pass_rounds_and_end_words for zip_write, which stages 512 rows a
+    round: 24 + 2049 x 16 bytes are three rounds in the second span, 8 mod 16 in all; capacities inside a
+    row, on and off a multiple of 8.  (A value across several spans: test_mixed_and_value_sizes.)"""
+    src = source(dev, "nulls", 2050)
+    picks = [(1, "s")]
+    w = model([src, src], picks)
+    total = len(w.data)
+    assert total == 24 + 2049 * 16 and total % 16 == 8 and not w.bad
+    for out_shift in (0, 8):
+        for cap in (None, total - 24, total - 20):
+            check_zip([src, src], picks, f"nulls shift {out_shift} capacity {cap}", cap=cap,
+                      out_shift=out_shift, want=w)
+    src.enc.device_status()
 
 
 def test_fixed_capacity_and_measure_form(dev):
