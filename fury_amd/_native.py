@@ -49,6 +49,15 @@ class FuryZipSource(ctypes.Structure):
 
 ZIP_MAX_SOURCES = 4
 
+
+class FuryConcatSource(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("row_offsets", ctypes.c_void_p),
+                ("nrows", ctypes.c_int64)]
+
+
+PARTITION_MAX_PARTS = 65535
+CONCAT_MAX_SOURCES = 32
+
 # Exported symbols with their signatures (kept in sync with include/fury_row.h; the CPU test
 # suite checks the header and this table agree).
 _P = ctypes.c_void_p
@@ -82,6 +91,9 @@ SIGNATURES = {
                                        ctypes.POINTER(FuryColumn), _P, _P]),
     "fury_row_take": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     "fury_row_filter": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P]),
+    "fury_row_partition": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P]),
+    "fury_row_concat": (ctypes.c_int, [_P, ctypes.POINTER(FuryConcatSource), _I32, _P, _I64, _P,
+                                       _P]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

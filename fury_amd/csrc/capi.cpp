@@ -1290,6 +1290,95 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
   return launch_filter(a, row_mask, out_count, out_indices, hs);
 }
 
+// Rows split by a per-row partition id (partition.hip): filter from 2 ways to num_parts ways.
+int fury_row_partition(const fury_schema* s, const void* rows, const int64_t* row_offsets,
+                       int64_t nrows, const int32_t* part_ids, int32_t num_parts, void* out_rows,
+                       int64_t out_capacity, int64_t* out_offsets, int64_t* out_part_rows,
+                       int64_t* out_indices, int64_t* out_positions, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_partition");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  if (num_parts < 1 || num_parts > FURY_PARTITION_MAX_PARTS)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_parts " + std::to_string(num_parts) + " is not in [1, " +
+                         std::to_string(FURY_PARTITION_MAX_PARTS) + "]");
+  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  if (nrows > 0 && !part_ids) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": part_ids is null");
+  if (misaligned(part_ids, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": part_ids must be 4-byte aligned");
+  if (!out_part_rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_part_rows is null");
+  if (misaligned(out_part_rows, 8) || misaligned(out_indices, 8) || misaligned(out_positions, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": out_part_rows / out_indices / out_positions must be 8-byte aligned");
+  TakeArgs a;
+  int st = take_args(s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, f, &a);
+  if (st) return st;
+  st = take_device_error(hs);
+  if (st) return st;
+  a.n = nrows;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_partition(a, part_ids, num_parts, out_part_rows, out_indices, out_positions, hs);
+}
+
+// Batches of one schema end to end (partition.hip): the vertical counterpart of fury_row_zip.
+int fury_row_concat(const fury_schema* s, const fury_concat_source* sources, int32_t num_sources,
+                    void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_concat");
+  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (!sources) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the source table is null");
+  if (num_sources < 1 || num_sources > FURY_CONCAT_MAX_SOURCES)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_sources " + std::to_string(num_sources) + " is not in [1, " +
+                         std::to_string(FURY_CONCAT_MAX_SOURCES) + "]");
+  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
+  if (misaligned(out_rows, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
+  if (misaligned(out_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets must be 8-byte aligned");
+  ConcatArgs a{};
+  for (int32_t k = 0; k < num_sources; k++) {
+    const fury_concat_source& c = sources[k];
+    const std::string src = f + ": source " + std::to_string(k);
+    if (c.nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": nrows < 0");
+    if (c.nrows > INT64_MAX - a.base[k]) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": batch too large");
+    a.base[k + 1] = a.base[k] + c.nrows;
+    if (c.nrows == 0) continue;       // an empty source is never read
+    if (!c.rows) return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows is null");
+    if (misaligned(c.rows, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows must be 8-byte aligned");
+    if (!s->is_fixed && !c.row_offsets)
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": variable-length rows need row_offsets");
+    if (misaligned(c.row_offsets, 8))
+      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": row_offsets must be 8-byte aligned");
+    a.rows[k] = static_cast<const uint8_t*>(c.rows);
+    a.ro[k] = s->is_fixed ? nullptr : c.row_offsets;    // fixed schemas: row i at i * fixed_size
+  }
+  const int64_t n = a.base[num_sources];
+  int st = too_large(n, s->fixed_size);
+  if (st) return set_error(st, f + ": batch too large");
+  if (!s->is_fixed && !out_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need out_offsets");
+  if (s->is_fixed && out_rows && s->fixed_size > 0 && out_capacity / s->fixed_size < n)
+    return set_error(FURY_ERR_CAPACITY,
+                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(n) +
+                         " rows of " + std::to_string(s->fixed_size) + " bytes");
+  st = take_device_error(hs);
+  if (st) return st;
+  a.nsrc = num_sources;
+  a.fixed = s->is_fixed ? 1 : 0;
+  a.fixed_size = s->fixed_size;
+  a.n = n;
+  a.out = static_cast<uint8_t*>(out_rows);
+  a.cap = out_rows ? out_capacity : 0;
+  a.out_offsets = out_offsets;
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  return launch_concat(a, hs);
+}
+
 // A subset of the fields, as rows (select.hip): BinaryRow's getters feeding a BinaryRowWriter of the
 // selected schema.  The host turns the selection into the int32 table SelectArgs describes.
 int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_selected,

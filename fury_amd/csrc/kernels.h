@@ -321,6 +321,44 @@ int launch_take(const TakeArgs& a, hipStream_t stream);
 // holds the kept row numbers and -1 past the count.  The count is never read by the host.
 int launch_filter(const TakeArgs& a, const uint8_t* row_mask, int64_t* out_count,
                   int64_t* out_indices, hipStream_t stream);
+// FURY_ERR_INVALID_ARGUMENT ("batch too large") for a row count the selection kernels cannot index.
+int too_large(int64_t n, int64_t fixed_size);
+// The second half of a selection whose row list and count live on the device (filter, partition):
+// a.out_offsets[0, nrows) holds the sizes of the selected rows (0 at or past *count), idx[j] the
+// source row of output row j < *count.  Scans the offsets in place (sws: scan_workspace(nrows))
+// and copies; fixed-size rows: the offsets, when wanted, and the copy come from *count.
+void copy_selected(const TakeArgs& a, const int64_t* idx, const int64_t* count, int64_t* sws,
+                   hipStream_t stream);
+
+// ---- rows by key, batches end to end: partition.hip ----------------------------------------------
+// Stable P-way partition of a batch by a per-row id (filter from 2 ways to P): the kept rows (0 <=
+// part_ids[i] < num_parts) sorted by (id, source row).  out_part_rows[p] (num_parts + 1 entries) =
+// kept rows with id < p; out_indices / out_positions (optional, nrows entries) = the permutation and
+// its inverse, -1 at or past the count / for a dropped row.  a.out_offsets, capacity, bounds and the
+// fixed-size form as in launch_filter (a.n = nrows).  Nothing is read by the host.
+constexpr int kPartitionMaxParts = 65535;
+int launch_partition(const TakeArgs& a, const int32_t* part_ids, int32_t num_parts,
+                     int64_t* out_part_rows, int64_t* out_indices, int64_t* out_positions,
+                     hipStream_t stream);
+// Batches of one schema end to end: output row base[k] + i = row i of source k (base[k] = rows of
+// the sources before k, base[nsrc] = n).  ro[k] NULL: fixed-size rows.  A row is checked against
+// its own source's [0, ro[k][nrows_k]); a failing one has size 0 and raises kErrBounds with its
+// output position.  out NULL: the measure form.
+constexpr int kConcatMaxSources = 32;
+struct ConcatArgs {
+  const uint8_t* rows[kConcatMaxSources];
+  const int64_t* ro[kConcatMaxSources];
+  int64_t base[kConcatMaxSources + 1];
+  int32_t nsrc;
+  int32_t fixed;                      // fixed-size rows: every ro[k] is NULL
+  int64_t fixed_size;
+  int64_t n;
+  uint8_t* out;
+  int64_t cap;
+  int64_t* out_offsets;               // n + 1 entries; optional for fixed-size rows
+  uint32_t* err;
+};
+int launch_concat(const ConcatArgs& a, hipStream_t stream);
 
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each

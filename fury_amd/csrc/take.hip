@@ -39,17 +39,6 @@ namespace fury {
 
 namespace {
 
-// Size of source row i, *ok = false (size 0) when the row may not be read.
-__device__ __forceinline__ int64_t row_extent(const int64_t* ro, int64_t nrows, int64_t total,
-                                              int64_t i, bool* ok) {
-  *ok = false;
-  if (i < 0 || i >= nrows) return 0;
-  const int64_t b = gl(ro)[i], e = gl(ro)[i + 1];
-  if (e < b || !span_ok(b, e - b, total) || ((b | e) & 7)) return 0;
-  *ok = true;
-  return e - b;
-}
-
 __global__ __launch_bounds__(kTakeThreads) void take_sizes(const int64_t* __restrict__ ro,
                                                            int64_t nrows,
                                                            const int64_t* __restrict__ idx, int64_t n,
@@ -193,13 +182,6 @@ __global__ __launch_bounds__(kTakeThreads) void take_copy_fixed(const uint8_t* _
   }
 }
 
-int too_large(int64_t n, int64_t fixed_size) {
-  // blocks_of() in 31 bits, and the fixed copy's multiply-high exact
-  if (n >= (int64_t{1} << 38) || (fixed_size > 0 && n > (int64_t{1} << 52) / fixed_size))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
-  return FURY_OK;
-}
-
 void copy_fixed(const TakeArgs& a, const int64_t* idx, int64_t n, const int64_t* count,
                 hipStream_t stream) {
   const int64_t bytes = std::min(a.cap, n * a.fixed_size);
@@ -211,6 +193,29 @@ void copy_fixed(const TakeArgs& a, const int64_t* idx, int64_t n, const int64_t*
 }
 
 }  // namespace
+
+int too_large(int64_t n, int64_t fixed_size) {
+  // blocks_of() in 31 bits, and the fixed copy's multiply-high exact
+  if (n >= (int64_t{1} << 38) || (fixed_size > 0 && n > (int64_t{1} << 52) / fixed_size))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
+  return FURY_OK;
+}
+
+void copy_selected(const TakeArgs& a, const int64_t* idx, const int64_t* count, int64_t* sws,
+                   hipStream_t stream) {
+  const int64_t n = a.nrows;
+  if (!a.row_offsets) {
+    if (a.out_offsets)
+      hipLaunchKernelGGL(fixed_offsets, dim3(blocks_of(n + 1)), dim3(kTakeThreads), 0, stream,
+                         a.out_offsets, n, count, a.fixed_size);
+    copy_fixed(a, idx, n, count, stream);
+  } else {
+    device_scan(a.out_offsets, n, a.out_offsets + n, sws, stream);
+    if (a.out && a.cap >= 8)
+      hipLaunchKernelGGL(take_copy, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a.rows,
+                         a.row_offsets, idx, n, a.out, a.out_offsets, a.cap);
+  }
+}
 
 int launch_take(const TakeArgs& a, hipStream_t stream) {
   const int64_t n = a.n;
@@ -262,17 +267,7 @@ int launch_filter(const TakeArgs& a, const uint8_t* mask, int64_t* out_count, in
   device_scan(tc, nt, out_count, sws, stream);
   hipLaunchKernelGGL(filter_write, dim3(blocks_of(n)), dim3(kTakeThreads), 0, stream, mask,
                      a.row_offsets, n, tc, out_count, idx, fixed ? nullptr : a.out_offsets, a.err);
-  if (fixed) {
-    if (a.out_offsets)
-      hipLaunchKernelGGL(fixed_offsets, dim3(blocks_of(n + 1)), dim3(kTakeThreads), 0, stream,
-                         a.out_offsets, n, out_count, a.fixed_size);
-    copy_fixed(a, idx, n, out_count, stream);
-  } else {
-    device_scan(a.out_offsets, n, a.out_offsets + n, sws, stream);
-    if (a.out && a.cap >= 8)
-      hipLaunchKernelGGL(take_copy, dim3(copy_grid(a.cap)), dim3(kTakeThreads), 0, stream, a.rows,
-                         a.row_offsets, idx, n, a.out, a.out_offsets, a.cap);
-  }
+  copy_selected(a, idx, out_count, sws, stream);
   st = check_hip(hipGetLastError(), "filter launch");
   dev_free(ws, stream);
   return st;

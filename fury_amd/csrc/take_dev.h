@@ -1,11 +1,12 @@
 // take_dev.h -- the byte-balanced, output-parallel write pass of every operator that makes a row
 // batch, once: write_spans (the span loop, the row search, the staging rounds) and store_split (the
 // 16-byte alignment of a round's stores); the design is described in take.hip.  Its instances:
-//   copy_rows       a row is a run of source bytes: take.hip, extract.hip, explode.hip and map.hip's
-//                   split each give it their lookup of an output row's source start
+//   copy_rows       a row is a run of source bytes: take.hip, partition.hip's concat, extract.hip,
+//                   explode.hip and map.hip's split each give it their lookup of an output row's
+//                   source start
 //   select_write, zip_write              every 8-byte word is made on its own (store_words)
 //   implode_write, map_join_write        a word is generated or copied from a run (store_located)
-// take.hip includes it directly, the other files through select_dev.h or extract_dev.h.
+// take.hip and partition.hip include it directly, the other files through select_dev.h or extract_dev.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,6 +40,17 @@ __device__ __forceinline__ void st8(uint8_t* p, uint64_t v) {
 }
 __device__ __forceinline__ void st16(uint8_t* p, v2q v) {
   __builtin_nontemporal_store(v, gl(reinterpret_cast<v2q*>(p)));
+}
+
+// Size of source row i, *ok = false (size 0) when the row may not be read.
+__device__ __forceinline__ int64_t row_extent(const int64_t* ro, int64_t nrows, int64_t total,
+                                              int64_t i, bool* ok) {
+  *ok = false;
+  if (i < 0 || i >= nrows) return 0;
+  const int64_t b = gl(ro)[i], e = gl(ro)[i + 1];
+  if (e < b || !span_ok(b, e - b, total) || ((b | e) & 7)) return 0;
+  *ok = true;
+  return e - b;
 }
 
 // The largest j in [lo, lo + len) with oo[j] <= key, for a non-decreasing oo with oo[lo] <= key:

@@ -859,6 +859,166 @@ class RowEncoder:
         out = RowBatch(rows[:total], offs, count, self.schema_hash)
         return (out, kept) if return_indices else out
 
+    # -- rows by key, batches end to end (fury_row_partition / fury_row_concat) -------------------
+    def _part_ids(self, part_ids, nrows: int, stream) -> torch.Tensor:
+        """``part_ids`` as the device int32 tensor the kernels read: a value outside int32 becomes
+        -1 before narrowing, so it drops its row instead of wrapping into a partition."""
+        if not isinstance(part_ids, torch.Tensor):
+            a = np.asarray(part_ids)
+            if a.size == 0:                    # an empty list has no dtype of its own
+                a = a.astype(np.int32)
+            if a.dtype.kind not in "iu":
+                raise IllegalArgumentException(f"part_ids must be integers, not {a.dtype}")
+            if a.dtype.kind == "u" and a.dtype.itemsize >= 4:      # torch has no wide unsigned
+                a = np.where(a > np.iinfo(np.int32).max, -1, a.astype(np.int64))
+            part_ids = torch.as_tensor(np.ascontiguousarray(a))
+        if part_ids.dtype.is_floating_point or part_ids.dtype.is_complex or \
+                part_ids.dtype == torch.bool:
+            raise IllegalArgumentException(
+                f"part_ids must be an integer tensor, not {part_ids.dtype}")
+        if part_ids.numel() != nrows:
+            raise IllegalArgumentException(f"part_ids has {part_ids.numel()} entries for {nrows} rows")
+        with _on(stream):
+            ids = part_ids.to(self.device).reshape(-1)
+            if ids.dtype == torch.int64:
+                lim = torch.iinfo(torch.int32)
+                ids = torch.where((ids < lim.min) | (ids > lim.max), -1, ids)
+            return ids.to(torch.int32).contiguous()
+
+    def _partition_args(self, batch: RowBatch, part_ids, num_parts, out_rows, out_offsets,
+                        out_part_rows, out_indices, out_positions, stream, keep: list):
+        self._check_hash(batch)
+        ids = self._part_ids(part_ids, batch.nrows, stream)
+        keep.append(ids)
+        return (self._schema.handle, _ptr(batch.rows), _ptr(batch.row_offsets), batch.nrows,
+                _ptr(ids), int(num_parts), _ptr(out_rows), _nbytes(out_rows), _ptr(out_offsets),
+                _ptr(out_part_rows), _ptr(out_indices), _ptr(out_positions),
+                _stream_handle(stream))
+
+    def partition_into(self, batch: RowBatch, part_ids, num_parts: int,
+                       out_rows: Optional[torch.Tensor], out_offsets: Optional[torch.Tensor],
+                       out_part_rows: torch.Tensor, out_indices: Optional[torch.Tensor] = None,
+                       out_positions: Optional[torch.Tensor] = None, stream=None) -> None:
+        """Splits the rows of ``batch`` by ``part_ids`` (any integer tensor or array, ``nrows``
+        entries): row i is kept when ``0 <= part_ids[i] < num_parts`` and dropped otherwise, and
+        the kept rows come out sorted by (id, row number) -- each partition contiguous and in
+        source order.  One call, no host synchronisation.  ``out_part_rows`` (int64,
+        ``num_parts + 1`` entries) receives the first output row of every partition and the count
+        of kept rows last; ``out_offsets`` (int64, nrows + 1 entries; optional for fixed-width
+        schemas) the offsets, entries past the count repeating the total; ``out_indices`` /
+        ``out_positions`` (optional, int64, nrows entries) the source row of every output position
+        and the output position of every source row, -1 past the count / for a dropped row.
+        Capacity and ``out_rows=None`` as in ``take_into``."""
+        keep: list = []
+        _check(N.lib().fury_row_partition(*self._partition_args(
+            batch, part_ids, num_parts, out_rows, out_offsets, out_part_rows, out_indices,
+            out_positions, stream, keep)))
+
+    def bind_partition(self, batch: RowBatch, part_ids, num_parts: int,
+                       out_rows: Optional[torch.Tensor], out_offsets: Optional[torch.Tensor],
+                       out_part_rows: torch.Tensor, out_indices: Optional[torch.Tensor] = None,
+                       out_positions: Optional[torch.Tensor] = None, stream=None):
+        """``partition_into`` bound like ``bind_take``: pointers resolved once (``part_ids`` is
+        converted now; an int32 device tensor is read in place by every call)."""
+        keep: list = []
+        fn = N.lib().fury_row_partition
+        args = self._partition_args(batch, part_ids, num_parts, out_rows, out_offsets,
+                                    out_part_rows, out_indices, out_positions, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_rows, out_offsets, out_part_rows, out_indices, out_positions,
+                     self, self._schema)
+        return call
+
+    def partition(self, batch: RowBatch, part_ids, num_parts: int, stream=None,
+                  return_indices: bool = False):
+        """``(RowBatch of the kept rows in partition order, part_rows[num_parts + 1])`` (with
+        ``return_indices``: and their source row numbers).  The ids are ranked and measured on the
+        device, count and byte total come back in one host read, then the kept rows are copied.
+        Partition p is ``slice_rows(out, part_rows[p], part_rows[p + 1])``."""
+        self._check_hash(batch)
+        n = batch.nrows
+        fixed = self._schema.is_fixed
+        ids = self._part_ids(part_ids, n, stream)
+        with _on(stream):
+            part_rows = torch.empty(num_parts + 1 if num_parts > 0 else 1, dtype=torch.int64,
+                                    device=self.device)
+            idx = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+            offs = None if fixed else torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            self.partition_into(batch, ids, num_parts, None, offs, part_rows,
+                                idx[:n] if n else None, None, stream)
+            if fixed:
+                count = int(part_rows[num_parts].item())
+                total = count * self._schema.fixed_size
+            else:
+                count, total = (int(x) for x in torch.stack((part_rows[num_parts], offs[n])).cpu())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            kept = idx[:count]
+            offs = None if fixed else offs[:count + 1]
+        self.take_into(batch, kept, rows, offs, stream)
+        self.device_status(stream)
+        out = RowBatch(rows[:total], offs, count, self.schema_hash)
+        return (out, part_rows, kept) if return_indices else (out, part_rows)
+
+    def slice_rows(self, batch: RowBatch, start: int, stop: int) -> RowBatch:
+        """Rows ``[start, stop)`` of ``batch`` as a batch: ``rows`` is a view (no copy), the
+        offsets are rebased to start at 0 (``None`` for fixed-width schemas).  One host read of the
+        two byte positions for a variable-length schema."""
+        self._check_hash(batch)
+        start, stop = int(start), int(stop)
+        if not 0 <= start <= stop <= batch.nrows:
+            raise IndexOutOfBoundsException(
+                f"rows [{start}, {stop}) are not inside a batch of {batch.nrows} rows")
+        if self._schema.is_fixed or batch.row_offsets is None:
+            fs = self._schema.fixed_size
+            return RowBatch(batch.rows[start * fs:stop * fs], None, stop - start, self.schema_hash)
+        offs = batch.row_offsets[start:stop + 1]
+        b, e = (int(x) for x in offs[[0, -1]].cpu())
+        return RowBatch(batch.rows[b:e], offs - b, stop - start, self.schema_hash)
+
+    def _concat_args(self, batches: Sequence[RowBatch], out_rows, out_offsets, stream, keep: list):
+        for b in batches:
+            self._check_hash(b)
+        tab = (N.FuryConcatSource * max(len(batches), 1))()
+        for k, b in enumerate(batches):
+            tab[k].rows = _ptr(b.rows) if b.nrows else None
+            tab[k].row_offsets = _ptr(b.row_offsets)
+            tab[k].nrows = b.nrows
+        keep.append(tab)
+        return (self._schema.handle, tab, len(batches), _ptr(out_rows), _nbytes(out_rows),
+                _ptr(out_offsets), _stream_handle(stream))
+
+    def concat_into(self, batches: Sequence[RowBatch], out_rows: Optional[torch.Tensor],
+                    out_offsets: Optional[torch.Tensor] = None, stream=None) -> None:
+        """The rows of ``batches`` (1 to 32 batches of this encoder's schema) end to end, written
+        to the preallocated ``out_rows`` with their offsets in ``out_offsets`` (int64, total rows
+        + 1 entries; optional for fixed-width schemas): one call, no host synchronisation.  A
+        batch's offsets need not start at 0.  Capacity and ``out_rows=None`` as in ``take_into``;
+        a row outside its own batch gives a 0-byte row, reported by ``device_status(stream)``.
+        ``out_rows`` must not overlap any of the batches."""
+        keep: list = []
+        _check(N.lib().fury_row_concat(*self._concat_args(batches, out_rows, out_offsets, stream,
+                                                          keep)))
+
+    def concat(self, batches: Sequence[RowBatch], stream=None) -> RowBatch:
+        """``batches`` end to end as a new batch.  Fixed-width schemas know the size up front; the
+        others measure first (one host read of the byte total), then copy."""
+        batches = list(batches)
+        n = sum(b.nrows for b in batches)
+        with _on(stream):
+            if self._schema.is_fixed:
+                offs = None
+                total = n * self._schema.fixed_size
+            else:
+                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                self.concat_into(batches, None, offs, stream)
+                total = int(offs[n].item())
+            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+        self.concat_into(batches, rows, offs, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, self.schema_hash)
+
     # -- field selection: a subset of the fields, as rows (getters feeding a BinaryRowWriter) -----
     def selected_encoder(self, select: Sequence) -> "RowEncoder":
         """The ``RowEncoder`` of the fields ``select`` (names or slot indices, in selection order,

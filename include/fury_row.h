@@ -350,6 +350,73 @@ int fury_row_filter(const fury_schema* schema, const void* rows, const int64_t* 
                     void* out_rows, int64_t out_capacity, int64_t* out_offsets,
                     int64_t* out_count, int64_t* out_indices, void* stream);
 
+/* Rows by key, batches end to end -- BinaryRow.copy() over a batch again (FMT/row/binary/
+ * BinaryRow.java:173-179): a row is its bytes, unchanged, at a new position, so `schema` may be
+ * anything the library creates (flat, wide, nested, a collection schema).
+ *
+ * fury_row_partition: fury_row_filter from 2 ways to num_parts ways, 1 <= num_parts <=
+ * FURY_PARTITION_MAX_PARTS (the ids and one drop bucket fit 16 bits).  part_ids is device int32 with
+ * nrows entries.  Row i is KEPT when 0 <= part_ids[i] < num_parts; any other value, negative or too
+ * large, DROPS the row as a 0 mask bit does in filter, and a dropped row's extent is never examined.
+ * The kept rows come out sorted by (partition id, source row number) -- a stable partition -- so each
+ * partition's rows are contiguous and in source order; count = the number of kept rows.
+ *   out_part_rows  (device int64, num_parts + 1 entries, required) out_part_rows[p] = the number of
+ *                  kept rows with id < p, out_part_rows[num_parts] = count.  Partition p is output
+ *                  rows [out_part_rows[p], out_part_rows[p + 1]), its bytes are
+ *                  [out_offsets[out_part_rows[p]], out_offsets[out_part_rows[p + 1]]).  The host never
+ *                  reads it.
+ *   out_offsets    nrows + 1 entries: [0, count] are the scan of the kept rows' sizes in output order,
+ *                  (count, nrows] repeat out_offsets[count], exactly as filter does.
+ *   out_indices    (optional, nrows entries) the source row of output position j < count, -1 at or
+ *                  past the count.
+ *   out_positions  (optional, nrows entries) the output position of source row i, -1 for a dropped
+ *                  row: the inverse permutation.  fury_row_take of the partitioned batch at the
+ *                  positions of the kept rows restores source order.
+ * Every entry of every output array is written exactly once per call: the buffers are deterministic.
+ * Capacity, the measure form (out_rows == NULL), alignment, the no-overlap rule and the "batch too
+ * large" limit are those of fury_row_filter.  is_fixed schemas follow filter's rules too: row_offsets
+ * is ignored and may be NULL, out_offsets may be NULL (when given, out_offsets[j] = min(j, count) *
+ * fixed_size), and out_rows != NULL with out_capacity < nrows * fixed_size returns FURY_ERR_CAPACITY
+ * before any device work.  Bounds: a kept source row whose extent fails the rule of fury_row_take /
+ * fury_row_filter has size 0 -- it still occupies its output position -- and raises
+ * FURY_ERR_OUT_OF_BOUNDS on `stream`, naming that source row.  nrows == 0: out_part_rows is all zeros
+ * and out_offsets[0] = 0 (when given).  Asynchronous on `stream` with no host synchronisation.
+ * Argument errors are returned before any device work, a pending device error of `stream` after them
+ * and before the call's own work.
+ * Consequences: (a) the output equals fury_row_take with the stable argsort of the kept ids;
+ * (b) with num_parts == 1 and part_ids[i] = mask_bit(i) - 1, out_rows, out_offsets, out_part_rows[1]
+ * and out_indices equal fury_row_filter's out_rows, out_offsets, *out_count and out_indices byte for
+ * byte.
+ *
+ * fury_row_concat: glues 1 <= num_sources <= FURY_CONCAT_MAX_SOURCES batches of `schema` end to end,
+ * the vertical counterpart of fury_row_zip.  With N = the sum of the sources' nrows and R_k = the sum
+ * over the sources before source k, output row R_k + i is the bytes of row i of source k; out_offsets
+ * has N + 1 entries.  A source's row_offsets[0] need not be 0 (an interior slice of a larger batch
+ * with its offsets as they are).  Each source row obeys take's extent rule against ITS OWN source's
+ * [0, row_offsets_k[nrows_k]); a failing row has size 0 (is_fixed schemas: cannot fail) and raises
+ * FURY_ERR_OUT_OF_BOUNDS naming the output position.  Sources may alias each other; out_rows overlaps
+ * none of them.  Capacity, the measure form, the is_fixed form (out_offsets optional, FURY_ERR_CAPACITY
+ * up front when out_capacity < N * fixed_size) and N == 0 follow fury_row_take.  No host
+ * synchronisation: the sources' byte totals stay on the device.  Argument errors are returned before
+ * any device work.
+ * Consequences: concat of the num_parts slices of a partitioned batch, in partition order, returns
+ * the partitioned batch's first count rows byte for byte; concat of one source equals fury_row_take
+ * with indices 0, 1, ..., nrows - 1. */
+#define FURY_PARTITION_MAX_PARTS 65535
+int fury_row_partition(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
+                       int64_t nrows, const int32_t* part_ids, int32_t num_parts,
+                       void* out_rows, int64_t out_capacity, int64_t* out_offsets,
+                       int64_t* out_part_rows, int64_t* out_indices, int64_t* out_positions,
+                       void* stream);
+#define FURY_CONCAT_MAX_SOURCES 32
+typedef struct fury_concat_source {
+  const void* rows;            /* device, 8-byte aligned; may be NULL when nrows == 0 */
+  const int64_t* row_offsets;  /* nrows + 1 entries; ignored (may be NULL) when schema is_fixed */
+  int64_t nrows;
+} fury_concat_source;
+int fury_row_concat(const fury_schema* schema, const fury_concat_source* sources, int32_t num_sources,
+                    void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
