@@ -6,4 +6,24 @@ HIP kernels behind the C ABI in include/fury_row.h (libfury_row.so, built in-tre
 """
 from . import types  # noqa: F401
 
-__all__ = ["types"]
+__all__ = ["types", "hash_bytes", "hash_null"]
+
+
+def hash_bytes(b, seed: int = 0) -> int:
+    """MurmurHash3_x86_32 of the bytes ``b`` (rule 1 of fury_row_hash in include/fury_row.h): the
+    hash ``RowEncoder.hash_rows`` gives a non-null key with these value bytes, on the host.  Chain
+    the keys of a row as the device does: ``h = seed``, then ``h = hash_bytes(value, h)`` or
+    ``h = hash_null(h)`` per key, and ``h % num_parts`` is the row's partition."""
+    from . import _native as N
+    b = bytes(b)
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError(f"seed {seed} is not an unsigned 32-bit value")
+    return int(N.lib().fury_hash_bytes(b, len(b), int(seed)))
+
+
+def hash_null(seed: int = 0) -> int:
+    """The hash of a null key after ``seed`` (rule 2 of fury_row_hash)."""
+    from . import _native as N
+    if not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError(f"seed {seed} is not an unsigned 32-bit value")
+    return int(N.lib().fury_hash_null(int(seed)))

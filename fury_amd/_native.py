@@ -63,6 +63,7 @@ CONCAT_MAX_SOURCES = 32
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
+_U32 = ctypes.c_uint32
 SIGNATURES = {
     "fury_abi_version": (_I32, []),
     "fury_last_error": (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t]),
@@ -94,6 +95,10 @@ SIGNATURES = {
     "fury_row_partition": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P]),
     "fury_row_concat": (ctypes.c_int, [_P, ctypes.POINTER(FuryConcatSource), _I32, _P, _I64, _P,
                                        _P]),
+    "fury_row_hash": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _U32, _I32, _P, _P,
+                                     _P]),
+    "fury_hash_bytes": (_U32, [_P, _I64, _U32]),
+    "fury_hash_null": (_U32, [_U32]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

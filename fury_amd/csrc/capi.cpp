@@ -1157,6 +1157,84 @@ int fury_row_project_measure(const fury_schema* s, const int32_t* fields, int32_
                                 s->is_fixed ? nullptr : row_offsets, hs);
 }
 
+// Key hash (hash.hip): BinaryRow's getters feeding MurmurHash3.murmurhash3_x86_32, key after key.
+int fury_row_hash(const fury_schema* s, const int32_t* fields, int32_t num_keys, const void* rows,
+                  const int64_t* row_offsets, int64_t nrows, uint32_t seed, int32_t num_parts,
+                  uint32_t* out_hashes, int32_t* out_part_ids, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_hash");
+  // `fields` stands in for the column table check_selection wants: this call has none
+  int st = check_selection(s, fields, num_keys, nrows, fields, f,
+                           "has no row fields to hash",
+                           "there is no route (the seed is per call, not per row): hash a subset of the keys");
+  if (st) return st;
+  for (int j = 0; j < num_keys; j++) {
+    const int32_t k = fields[j];
+    if (s->plan[k].kind == kOther || s->plan[k].kind == kListFixed)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name +
+                           ") is a LIST / STRUCT / MAP: its stored bytes are not canonical (null "
+                           "slots keep stale contents), so it cannot be a hash key");
+  }
+  if (!out_hashes && !out_part_ids)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_hashes and out_part_ids are both null");
+  if (out_part_ids && num_parts < 1)
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": num_parts " + std::to_string(num_parts) + " is not in [1, 2147483647]");
+  if (misaligned(out_hashes, 4) || misaligned(out_part_ids, 4))
+    return set_error(FURY_ERR_INVALID_ARGUMENT,
+                     f + ": out_hashes / out_part_ids must be 4-byte aligned");
+  if (nrows == 0) return FURY_OK;
+  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
+  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
+  if (!s->is_fixed && !row_offsets)
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
+  if (misaligned(row_offsets, 8))
+    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets must be 8-byte aligned");
+  st = take_device_error(hs);
+  if (st) return st;
+  ProjArgs a{};
+  a.ncols = num_keys;
+  a.bitmap_bytes = s->bitmap_bytes;
+  a.fixed_size = s->fixed_size;
+  a.nrows = nrows;
+  a.nt = 1;
+  for (int j = 0; j < num_keys; j++) {
+    const FieldPlan& p = s->plan[fields[j]];
+    ProjCol& v = a.col[j];
+    v.kind = p.kind;
+    v.slot = fields[j];
+    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+  }
+  st = device_error_word(hs, &a.err);
+  if (st) return st;
+  // fixed schemas: row i at i * fixed_size, as in fury_row_project
+  return launch_hash(a, static_cast<const uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, seed,
+                     out_part_ids ? static_cast<uint32_t>(num_parts) : 1u, out_hashes, out_part_ids, hs);
+}
+
+// H of rule 1 on the host: a CPU worker routes a lookup key to the partition the device chose.
+uint32_t fury_hash_bytes(const void* bytes, int64_t len, uint32_t seed) {
+  if (len < 0 || len > INT32_MAX || (len > 0 && !bytes)) {
+    set_error(FURY_ERR_INVALID_ARGUMENT,
+              "fury_hash_bytes: len " + std::to_string(len) + " is not in [0, 2147483647] or bytes is null");
+    return 0;
+  }
+  const uint8_t* p = static_cast<const uint8_t*>(bytes);
+  uint32_t h = seed;
+  const int64_t nb = len >> 2;
+  for (int64_t i = 0; i < nb; i++)
+    h = mm3_block(h, static_cast<uint32_t>(p[4 * i]) | static_cast<uint32_t>(p[4 * i + 1]) << 8 |
+                         static_cast<uint32_t>(p[4 * i + 2]) << 16 |
+                         static_cast<uint32_t>(p[4 * i + 3]) << 24);
+  uint32_t k = 0;
+  for (int64_t i = len - 1; i >= 4 * nb; i--) k = (k << 8) | p[i];
+  if (len & 3) h = mm3_tail(h, k);
+  return mm3_fmix(h ^ static_cast<uint32_t>(len));
+}
+
+uint32_t fury_hash_null(uint32_t seed) { return mm3_null(seed); }
+
 // In-place update of selected fixed-width fields (update.hip): BinaryRow's setters over a batch.
 int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_selected, void* rows,
                     const int64_t* row_offsets, int64_t nrows, const fury_column* cols,

@@ -360,6 +360,38 @@ struct ConcatArgs {
 };
 int launch_concat(const ConcatArgs& a, hipStream_t stream);
 
+// ---- key hash of a row batch: hash.hip -------------------------------------------------------------
+// MurmurHash3_x86_32, the function the reference ships as MurmurHash3.murmurhash3_x86_32: 4-byte
+// little-endian blocks, a 1-3 byte tail, fmix32(h ^ len).  One definition for the host entry points
+// (fury_hash_bytes / fury_hash_null, capi.cpp) and the kernels.
+__host__ __device__ inline uint32_t mm3_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+__host__ __device__ inline uint32_t mm3_scramble(uint32_t k) {
+  return mm3_rotl(k * 0xcc9e2d51u, 15) * 0x1b873593u;
+}
+__host__ __device__ inline uint32_t mm3_block(uint32_t h, uint32_t k) {
+  return mm3_rotl(h ^ mm3_scramble(k), 13) * 5u + 0xe6546b64u;
+}
+// `k`: the 1-3 tail bytes, zero-extended.
+__host__ __device__ inline uint32_t mm3_tail(uint32_t h, uint32_t k) { return h ^ mm3_scramble(k); }
+__host__ __device__ inline uint32_t mm3_fmix(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  return h ^ (h >> 16);
+}
+// A null key: a zero-length value whose length word is 0xFFFFFFFF (rule 2 of fury_row_hash).
+__host__ __device__ inline uint32_t mm3_null(uint32_t h) { return mm3_fmix(h ^ 0xffffffffu); }
+
+// hash[r] = the chain of rule 2 over the a.ncols key fields of row r in a.col order (ProjCol.kind /
+// .width / .slot; the output members are unused), part_id[r] = (int32)(hash[r] % num_parts).  Either
+// output may be NULL.  Bounds = "Decode bounds" above as the projected decode applies them: a row
+// that fails row_ok has every key null, a value whose span fails is null, both raise kErrBounds with
+// the row; every entry of the given outputs is written.  row_offsets NULL: fixed-size rows.
+// Asynchronous on `stream`, no workspace.
+int launch_hash(const ProjArgs& a, const uint8_t* rows, const int64_t* row_offsets, uint32_t seed,
+                uint32_t num_parts, uint32_t* out_hashes, int32_t* out_part_ids, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

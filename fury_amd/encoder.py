@@ -1019,6 +1019,86 @@ class RowEncoder:
         self.device_status(stream)
         return RowBatch(rows[:total], offs, n, self.schema_hash)
 
+    # -- key hash: key fields of every row -> hash and partition id (fury_row_hash) ----------------
+    def _hash_args(self, batch: RowBatch, keys: Sequence, out_hashes, out_part_ids, seed, num_parts,
+                   stream, keep: list):
+        self._check_hash(batch)
+        idx = self._select(keys)
+        for what, t in (("out_hashes", out_hashes), ("out_part_ids", out_part_ids)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32):
+                raise IllegalArgumentException(f"{what} must be an int32 or uint32 tensor")
+            if t.numel() < batch.nrows:
+                raise IllegalArgumentException(
+                    f"{what} has {t.numel()} entries for {batch.nrows} rows")
+        seed = int(seed)
+        if not 0 <= seed <= 0xFFFFFFFF:
+            raise IllegalArgumentException(f"seed {seed} is not an unsigned 32-bit value")
+        if out_part_ids is None:
+            num_parts = 0                       # unused by the call
+        elif num_parts is None or not 1 <= int(num_parts) <= 0x7FFFFFFF:
+            raise IllegalArgumentException(f"num_parts {num_parts} is not in [1, 2**31 - 1]")
+        sel = (ctypes.c_int32 * max(len(idx), 1))(*idx)
+        keep.append(sel)
+        return (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
+                batch.nrows, seed, int(num_parts), _ptr(out_hashes), _ptr(out_part_ids),
+                _stream_handle(stream))
+
+    def hash_rows_into(self, batch: RowBatch, keys: Sequence, out_hashes: Optional[torch.Tensor],
+                       out_part_ids: Optional[torch.Tensor] = None, seed: int = 0,
+                       num_parts: Optional[int] = None, stream=None) -> None:
+        """Hashes the key fields ``keys`` (names or slot indices, in key order; 1 to 64 fixed-width,
+        BOOL, DECIMAL, STRING or BINARY fields) of every row: MurmurHash3_x86_32 over the bytes
+        ``project_batch`` would decode for each key, each value's hash seeding the next, a null key
+        hashed as ``hash_null`` (the numbered rules are in ``include/fury_row.h``).
+        ``out_hashes`` (uint32 or int32, ``nrows`` entries) receives the hash, ``out_part_ids``
+        (int32, ``nrows`` entries) ``hash % num_parts``, the ids ``partition_into`` takes; either
+        may be ``None``, not both.  One call, no host synchronisation, no workspace.  A row or key
+        value outside the batch is a null key, reported by ``device_status(stream)``."""
+        keep: list = []
+        _check(N.lib().fury_row_hash(*self._hash_args(batch, keys, out_hashes, out_part_ids, seed,
+                                                      num_parts, stream, keep)))
+
+    def bind_hash(self, batch: RowBatch, keys: Sequence, out_hashes: Optional[torch.Tensor],
+                  out_part_ids: Optional[torch.Tensor] = None, seed: int = 0,
+                  num_parts: Optional[int] = None, stream=None):
+        """``hash_rows_into`` bound like ``bind_project``: keys and pointers resolved once."""
+        keep: list = []
+        fn = N.lib().fury_row_hash
+        args = self._hash_args(batch, keys, out_hashes, out_part_ids, seed, num_parts, stream, keep)
+
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, batch, out_hashes, out_part_ids, self, self._schema)
+        return call
+
+    def hash_rows(self, batch: RowBatch, keys: Sequence, seed: int = 0,
+                  num_parts: Optional[int] = None, stream=None):
+        """The uint32 hash of every row's key fields; with ``num_parts``: ``(hashes, part_ids)``,
+        ``part_ids`` int32 = ``hashes % num_parts``.  See ``hash_rows_into``."""
+        n = batch.nrows
+        with _on(stream):
+            hashes = torch.empty(n, dtype=torch.uint32, device=self.device)
+            ids = None if num_parts is None else torch.empty(n, dtype=torch.int32,
+                                                             device=self.device)
+        if n > 0:                                # an empty tensor has no address to pass
+            self.hash_rows_into(batch, keys, hashes, ids, seed, num_parts, stream)
+            self.device_status(stream)
+        return hashes if num_parts is None else (hashes, ids)
+
+    def partition_by(self, batch: RowBatch, keys: Sequence, num_parts: int, seed: int = 0,
+                     stream=None):
+        """``partition`` by the hash of the key fields: ``(out, part_rows)`` with every row in
+        partition ``hash_rows(batch, keys, seed) % num_parts``.  The ids are hashed and the rows
+        ranked on ``stream`` with no host synchronisation in between; ``num_parts`` is
+        ``partition``'s (at most 65535)."""
+        with _on(stream):
+            ids = torch.empty(batch.nrows, dtype=torch.int32, device=self.device)
+        if batch.nrows > 0:
+            self.hash_rows_into(batch, keys, None, ids, seed, num_parts, stream)
+        return self.partition(batch, ids, num_parts, stream)
+
     # -- field selection: a subset of the fields, as rows (getters feeding a BinaryRowWriter) -----
     def selected_encoder(self, select: Sequence) -> "RowEncoder":
         """The ``RowEncoder`` of the fields ``select`` (names or slot indices, in selection order,

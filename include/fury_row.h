@@ -417,6 +417,60 @@ typedef struct fury_concat_source {
 int fury_row_concat(const fury_schema* schema, const fury_concat_source* sources, int32_t num_sources,
                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream);
 
+/* Key hash -- the batch form of reading a row's key fields with BinaryRow's getters and feeding them
+ * to MurmurHash3.murmurhash3_x86_32 (fury-core util/MurmurHash3.java; the same function is in
+ * cpp/fury/thirdparty/MurmurHash3.cc): a 32-bit hash and a partition id per row, the ids
+ * fury_row_partition takes.  The definition is normative, so that a worker in any language routes a
+ * lookup key to the partition the device chose:
+ *   1. H(bytes, seed) is MurmurHash3_x86_32 over a byte string: h = seed; every whole 4-byte block,
+ *      read little-endian as k, gives k *= 0xcc9e2d51, k = rotl32(k, 15), k *= 0x1b873593, h ^= k,
+ *      h = rotl32(h, 13), h = h * 5 + 0xe6546b64; the 1-3 bytes left over, little-endian and
+ *      zero-extended as k, give k *= 0xcc9e2d51, k = rotl32(k, 15), k *= 0x1b873593, h ^= k; the
+ *      result is fmix32(h ^ len), fmix32(h): h ^= h >> 16, h *= 0x85ebca6b, h ^= h >> 13,
+ *      h *= 0xc2b2ae35, h ^= h >> 16.  All arithmetic is modulo 2^32.  Bit-identical to the
+ *      reference's murmurhash3_x86_32(byte[] data, int offset, int len, int seed).
+ *   2. For row r and the key fields fields[0 .. num_keys) IN THE GIVEN ORDER: h = seed; for each key
+ *      k, h = fmix32(h ^ 0xFFFFFFFF) when the field is null in row r, else h = H(value_bytes(k, r), h)
+ *      -- each value's hash seeds the next.  A null is a zero-length value whose length word is
+ *      0xFFFFFFFF, so null and the empty string differ.  hash[r] = h.
+ *   3. value_bytes are the bytes of the column value fury_row_project produces for the field.
+ *      BOOL: one byte, 0 or 1.  INT8 / INT16 / INT32 / FLOAT32 / DATE32 / INT64 / FLOAT64 / TIMESTAMP:
+ *      the value little-endian at its width (1 / 2 / 4 / 4 / 4 / 8 / 8 / 8 bytes).  Floats are hashed
+ *      as their raw bits: -0.0 and 0.0 hash differently, and so do NaNs of different payloads.
+ *      DECIMAL: the 16 value bytes.  STRING / BINARY: the payload bytes, of any length (none for the
+ *      empty string).
+ *   4. part_id[r] = (int32)(hash[r] % (uint32)num_parts), hash[r] taken as unsigned.
+ *   5. A LIST, STRUCT or MAP key returns FURY_ERR_UNSUPPORTED: their stored bytes are not canonical
+ *      (null slots keep stale contents), so equal values need not have equal bytes.
+ * fury_row_hash: 1 <= num_keys <= 64; the checks on `schema` and `fields` and their error codes are
+ * fury_row_project's (a collection schema or more than 64 keys FURY_ERR_UNSUPPORTED; num_keys <= 0, an
+ * index that is not a field, a field given twice FURY_ERR_INVALID_ARGUMENT).  out_hashes (device
+ * uint32, nrows entries) and out_part_ids (device int32, nrows entries) are each optional, but not
+ * both NULL; num_parts is used only when out_part_ids is given and must then be in [1, INT32_MAX].
+ * `rows` is device memory, 8-byte aligned; row_offsets is ignored and may be NULL for an is_fixed
+ * schema (row i at i * fixed_size), as in fury_row_take.  nrows == 0 does nothing.  The call is
+ * asynchronous on `stream`, never synchronises with the host and allocates no workspace.
+ * Bounds are those of fury_row_project: a row whose header leaves [0, row_offsets[nrows]) has every
+ * key null, a key value whose bytes leave it (or whose size is negative) is null, and both raise
+ * FURY_ERR_OUT_OF_BOUNDS on `stream` naming the row; the hash and id of such a row follow rule 2 with
+ * those nulls, so every entry of the given outputs is always written.  Nothing outside the batch is
+ * read, and a corrupt slot of a field that is not a key is never seen.
+ * Consequence: fury_row_hash equals rules 1-4 applied to the columns fury_row_project decodes for the
+ * same fields.
+ * Limits: MurmurHash3's chain is serial within a value, so one value is hashed by one lane however
+ * long it is; keys of several KB per row run at that lane's rate.
+ *
+ * fury_hash_bytes / fury_hash_null (host, no device work): H(bytes[0, len), seed) of rule 1 and
+ * fmix32(seed ^ 0xFFFFFFFF) of rule 2, for a CPU worker that routes a key the same way: chain them
+ * over the key's values as rule 2 does.  0 <= len <= INT32_MAX (bytes may be NULL when len == 0);
+ * otherwise fury_hash_bytes returns 0 and fury_last_error says why. */
+int fury_row_hash(const fury_schema* schema, const int32_t* fields, int32_t num_keys,
+                  const void* rows, const int64_t* row_offsets, int64_t nrows,
+                  uint32_t seed, int32_t num_parts,
+                  uint32_t* out_hashes, int32_t* out_part_ids, void* stream);
+uint32_t fury_hash_bytes(const void* bytes, int64_t len, uint32_t seed);
+uint32_t fury_hash_null(uint32_t seed);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
