@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 #include <string>
@@ -492,6 +493,95 @@ namespace {
 
 bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
+// ---- the row operators' argument checks -----------------------------------------------------------
+// What fury_row_hash ... fury_row_map_join check of their buffers, written once: an operator composes
+// its checks from these, after its own schema / path / selection checks.  Every message starts with
+// the entry point's name `f` (an empty f gives the bare message: the projected decode's wording).
+int invalid(const std::string& f, const std::string& what) {
+  return set_error(FURY_ERR_INVALID_ARGUMENT, f.empty() ? what : f + ": " + what);
+}
+
+int check_count(const std::string& f, const char* name, int64_t v) {
+  return v < 0 ? invalid(f, std::string(name) + " < 0") : FURY_OK;
+}
+
+int check_required(const std::string& f, const char* name, const void* p) {
+  return p ? FURY_OK : invalid(f, std::string(name) + " is null");
+}
+
+// Every pointer of the list is `a`-byte aligned (a null one is); the message names the whole list.
+struct NamedPtr {
+  const char* name;
+  const void* p;
+};
+int check_aligned(const std::string& f, uintptr_t a, std::initializer_list<NamedPtr> ptrs) {
+  bool bad = false;
+  std::string names;
+  for (const NamedPtr& n : ptrs) {
+    bad = bad || misaligned(n.p, a);
+    names += std::string(names.empty() ? "" : " / ") + n.name;
+  }
+  return bad ? invalid(f, names + " must be " + std::to_string(a) + "-byte aligned") : FURY_OK;
+}
+
+// How a source batch finds its rows: at i * fixed_size (row_offsets is ignored), or through row_offsets,
+// which the rows of a variable-length schema need, and the paths of extract, explode and map split
+// whatever the schema.
+enum SourceRows { kFixedRows, kVariableRows, kOffsetRows };
+SourceRows rows_of(const fury_schema* s) { return s->is_fixed ? kFixedRows : kVariableRows; }
+
+// A source batch; `read`: the call reads at least one of its rows.  The alignment of row_offsets is the
+// caller's: where an entry checks it, its message names further pointers.
+int check_source(const std::string& f, const void* rows, const int64_t* row_offsets, SourceRows how,
+                 bool read) {
+  if (misaligned(rows, 8)) return invalid(f, "rows must be 8-byte aligned");
+  if (how == kVariableRows && !row_offsets) return invalid(f, "variable-length rows need row_offsets");
+  if (how == kOffsetRows && !row_offsets) return invalid(f, "row_offsets is null");
+  if (read && !rows) return invalid(f, "rows is null");
+  return FURY_OK;
+}
+
+// ... into an argument block that names the members as TakeArgs does.
+template <class Args>
+int check_source(const std::string& f, const void* rows, const int64_t* row_offsets, SourceRows how,
+                 bool read, Args* a) {
+  a->rows = static_cast<const uint8_t*>(rows);
+  a->row_offsets = how == kFixedRows ? nullptr : row_offsets;    // row i at i * fixed_size
+  return check_source(f, rows, row_offsets, how, read);
+}
+
+// An output batch, into an argument block that names the members as TakeArgs does.  `need_offsets`: what
+// to say when out_offsets is null, or NULL when the output rows are `row_size` bytes each (row r at
+// r * row_size, out_offsets optional): `n` of them must then fit a buffer that is given.  The alignment
+// of out_offsets is the caller's, as check_source's.
+template <class Args>
+int check_output(const std::string& f, void* out_rows, int64_t out_capacity, int64_t* out_offsets, Args* a,
+                 const char* need_offsets, int64_t n = 0, int64_t row_size = 0) {
+  if (out_capacity < 0) return invalid(f, "out_capacity < 0");
+  if (misaligned(out_rows, 8)) return invalid(f, "out_rows must be 8-byte aligned");
+  if (need_offsets && !out_offsets) return invalid(f, need_offsets);
+  if (!need_offsets && out_rows && row_size > 0 && out_capacity / row_size < n)
+    return set_error(FURY_ERR_CAPACITY,
+                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(n) +
+                         " rows of " + std::to_string(row_size) + " bytes");
+  a->out = static_cast<uint8_t*>(out_rows);
+  a->cap = out_rows ? out_capacity : 0;      // no buffer: the measure form
+  a->out_offsets = out_offsets;
+  return FURY_OK;
+}
+constexpr const char* kNeedOutOffsets = "variable-length rows need out_offsets";
+constexpr const char* kOutOffsetsNull = "out_offsets is null";
+
+// The end of every row operator, after its last argument check: the stream's pending device error,
+// the error slot of this launch, the launch.
+template <class Args, class Launch>
+int launch_checked(hipStream_t hs, Args* a, Launch launch) {
+  int st = take_device_error(hs);
+  if (st) return st;
+  if ((st = device_error_word(hs, &a->err))) return st;
+  return launch();
+}
+
 int common_checks(const fury_schema* s, const void* cols, int64_t nrows, const char* fn,
                   hipStream_t hs) {
   if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, std::string(fn) + ": schema is null");
@@ -773,15 +863,6 @@ Selection make_selection(int32_t n, int stride, SchemaOf schema_of, FieldOf fiel
   sel.out_bitmap = bitmap_bytes(n);
   sel.out_fixed = sel.out_bitmap + 8 * static_cast<int64_t>(n);
   return sel;
-}
-
-// Rows of a fixed-width selection sit at r * out_fixed: the capacity is checked before the launch.
-int check_fixed_capacity(const Selection& sel, const void* out_rows, int64_t out_capacity,
-                         int64_t nrows, const std::string& f) {
-  if (!sel.var.empty() || !out_rows || out_capacity / sel.out_fixed >= nrows) return FURY_OK;
-  return set_error(FURY_ERR_CAPACITY,
-                   f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(nrows) +
-                       " rows of " + std::to_string(sel.out_fixed) + " bytes");
 }
 
 // What SelectArgs and ZipArgs say of the selection; the table is complete afterwards.
@@ -1113,10 +1194,7 @@ static int project_args(const fury_schema* s, const int32_t* fields, int32_t nse
     }
   }
   if (nrows == 0) return FURY_OK;
-  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows is null");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows must be 8-byte aligned");
-  if (!s->is_fixed && !row_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, "variable-length rows need row_offsets");
+  if ((st = check_source(std::string(), rows, row_offsets, rows_of(s), true))) return st;
   return device_error_word(hs, &a->err);
 }
 
@@ -1176,23 +1254,13 @@ int fury_row_hash(const fury_schema* s, const int32_t* fields, int32_t num_keys,
                            ") is a LIST / STRUCT / MAP: its stored bytes are not canonical (null "
                            "slots keep stale contents), so it cannot be a hash key");
   }
-  if (!out_hashes && !out_part_ids)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_hashes and out_part_ids are both null");
+  if (!out_hashes && !out_part_ids) return invalid(f, "out_hashes and out_part_ids are both null");
   if (out_part_ids && num_parts < 1)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": num_parts " + std::to_string(num_parts) + " is not in [1, 2147483647]");
-  if (misaligned(out_hashes, 4) || misaligned(out_part_ids, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": out_hashes / out_part_ids must be 4-byte aligned");
+    return invalid(f, "num_parts " + std::to_string(num_parts) + " is not in [1, 2147483647]");
+  if ((st = check_aligned(f, 4, {{"out_hashes", out_hashes}, {"out_part_ids", out_part_ids}}))) return st;
   if (nrows == 0) return FURY_OK;
-  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (!s->is_fixed && !row_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
-  if (misaligned(row_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets must be 8-byte aligned");
-  st = take_device_error(hs);
-  if (st) return st;
+  if ((st = check_source(f, rows, row_offsets, rows_of(s), true))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}}))) return st;
   ProjArgs a{};
   a.ncols = num_keys;
   a.bitmap_bytes = s->bitmap_bytes;
@@ -1206,11 +1274,11 @@ int fury_row_hash(const fury_schema* s, const int32_t* fields, int32_t num_keys,
     v.slot = fields[j];
     v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
   }
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
   // fixed schemas: row i at i * fixed_size, as in fury_row_project
-  return launch_hash(a, static_cast<const uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, seed,
-                     out_part_ids ? static_cast<uint32_t>(num_parts) : 1u, out_hashes, out_part_ids, hs);
+  return launch_checked(hs, &a, [&] {
+    return launch_hash(a, static_cast<const uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, seed,
+                       out_part_ids ? static_cast<uint32_t>(num_parts) : 1u, out_hashes, out_part_ids, hs);
+  });
 }
 
 // H of rule 1 on the host: a CPU worker routes a lookup key to the partition the device chose.
@@ -1253,8 +1321,7 @@ int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_sel
                            ") is not fixed-width: variable-length values cannot be updated in "
                            "place (re-encode the batch with fury_row_encode)");
   }
-  if (misaligned(row_mask, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask must be 4-byte aligned");
+  if ((st = check_aligned(f, 4, {{"row_mask", row_mask}}))) return st;
   st = take_device_error(hs);
   if (st) return st;
   ProjArgs a{};
@@ -1280,44 +1347,27 @@ int fury_row_update(const fury_schema* s, const int32_t* fields, int32_t num_sel
       return set_error(FURY_ERR_INVALID_ARGUMENT, who + ": values misaligned");
   }
   if (nrows == 0) return FURY_OK;
-  if (!rows) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows is null");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, "rows must be 8-byte aligned");
-  if (!s->is_fixed && !row_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, "variable-length rows need row_offsets");
+  if ((st = check_source(f, rows, row_offsets, rows_of(s), true))) return st;
   st = device_error_word(hs, &a.err);
   if (st) return st;
   // fixed schemas: row i at i * fixed_size, as in fury_row_project
   return launch_update(a, static_cast<uint8_t*>(rows), s->is_fixed ? nullptr : row_offsets, row_mask, hs);
 }
 
-// Row selection (take.hip): BinaryRow.copy() over a batch.  The host checks both calls share; `n` =
-// output rows the copy may have to produce (take: num_selected, filter: nrows).
-static int take_args(const fury_schema* s, const void* rows, const int64_t* row_offsets,
-                     int64_t nrows, int64_t n, void* out_rows, int64_t out_capacity,
-                     int64_t* out_offsets, const std::string& f, TakeArgs* a) {
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (!s->is_fixed && !row_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
-  if (!s->is_fixed && !out_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need out_offsets");
-  if (n > 0 && nrows > 0 && out_rows && !rows)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  if (s->is_fixed && out_rows && s->fixed_size > 0 && out_capacity / s->fixed_size < n)
-    return set_error(FURY_ERR_CAPACITY,
-                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(n) +
-                         " rows of " + std::to_string(s->fixed_size) + " bytes");
+// Row selection (take.hip): BinaryRow.copy() over a batch.  The source and output batch of take,
+// filter and partition; `n` = output rows the copy may have to produce (take: num_selected, the others:
+// nrows).
+static int take_args(const std::string& f, const fury_schema* s, const void* rows,
+                     const int64_t* row_offsets, int64_t nrows, int64_t n, void* out_rows,
+                     int64_t out_capacity, int64_t* out_offsets, TakeArgs* a) {
   *a = TakeArgs{};
-  a->rows = static_cast<const uint8_t*>(rows);
-  a->row_offsets = s->is_fixed ? nullptr : row_offsets;   // fixed schemas: row i at i * fixed_size
+  int st = check_output(f, out_rows, out_capacity, out_offsets, a,
+                        s->is_fixed ? nullptr : kNeedOutOffsets, n, s->fixed_size);
+  if (st) return st;
   a->nrows = nrows;
+  a->n = n;
   a->fixed_size = s->fixed_size;
-  a->out = static_cast<uint8_t*>(out_rows);
-  a->cap = out_rows ? out_capacity : 0;
-  a->out_offsets = out_offsets;
-  return FURY_OK;
+  return check_source(f, rows, row_offsets, rows_of(s), n > 0 && nrows > 0 && out_rows, a);
 }
 
 int fury_row_take(const fury_schema* s, const void* rows, const int64_t* row_offsets, int64_t nrows,
@@ -1325,23 +1375,17 @@ int fury_row_take(const fury_schema* s, const void* rows, const int64_t* row_off
                   int64_t out_capacity, int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_take");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (num_selected < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_selected < 0");
-  if (num_selected > 0 && !indices) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": indices is null");
-  if (misaligned(indices, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": indices must be 8-byte aligned");
+  int st = check_required(f, "schema", s);
+  if (st) return st;
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if ((st = check_count(f, "num_selected", num_selected))) return st;
+  if (num_selected > 0 && (st = check_required(f, "indices", indices))) return st;
+  if ((st = check_aligned(f, 8, {{"indices", indices}}))) return st;
   TakeArgs a;
-  int st = take_args(s, rows, row_offsets, nrows, num_selected, out_rows, out_capacity, out_offsets,
-                     f, &a);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
+  if ((st = take_args(f, s, rows, row_offsets, nrows, num_selected, out_rows, out_capacity, out_offsets, &a)))
+    return st;
   a.indices = indices;
-  a.n = num_selected;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_take(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_take(a, hs); });
 }
 
 int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_offsets,
@@ -1349,23 +1393,17 @@ int fury_row_filter(const fury_schema* s, const void* rows, const int64_t* row_o
                     int64_t* out_offsets, int64_t* out_count, int64_t* out_indices, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_filter");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (nrows > 0 && !row_mask) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask is null");
-  if (misaligned(row_mask, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_mask must be 4-byte aligned");
-  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
-  if (misaligned(out_count, 8) || misaligned(out_indices, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count / out_indices must be 8-byte aligned");
+  int st = check_required(f, "schema", s);
+  if (st) return st;
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if (nrows > 0 && (st = check_required(f, "row_mask", row_mask))) return st;
+  if ((st = check_aligned(f, 4, {{"row_mask", row_mask}}))) return st;
+  if ((st = check_required(f, "out_count", out_count))) return st;
+  if ((st = check_aligned(f, 8, {{"out_count", out_count}, {"out_indices", out_indices}}))) return st;
   TakeArgs a;
-  int st = take_args(s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, f, &a);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
-  a.n = nrows;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_filter(a, row_mask, out_count, out_indices, hs);
+  if ((st = take_args(f, s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, &a)))
+    return st;
+  return launch_checked(hs, &a, [&] { return launch_filter(a, row_mask, out_count, out_indices, hs); });
 }
 
 // Rows split by a per-row partition id (partition.hip): filter from 2 ways to num_parts ways.
@@ -1375,29 +1413,25 @@ int fury_row_partition(const fury_schema* s, const void* rows, const int64_t* ro
                        int64_t* out_indices, int64_t* out_positions, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_partition");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
+  int st = check_required(f, "schema", s);
+  if (st) return st;
+  if ((st = check_count(f, "nrows", nrows))) return st;
   if (num_parts < 1 || num_parts > FURY_PARTITION_MAX_PARTS)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": num_parts " + std::to_string(num_parts) + " is not in [1, " +
-                         std::to_string(FURY_PARTITION_MAX_PARTS) + "]");
-  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  if (nrows > 0 && !part_ids) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": part_ids is null");
-  if (misaligned(part_ids, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": part_ids must be 4-byte aligned");
-  if (!out_part_rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_part_rows is null");
-  if (misaligned(out_part_rows, 8) || misaligned(out_indices, 8) || misaligned(out_positions, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": out_part_rows / out_indices / out_positions must be 8-byte aligned");
+    return invalid(f, "num_parts " + std::to_string(num_parts) + " is not in [1, " +
+                          std::to_string(FURY_PARTITION_MAX_PARTS) + "]");
+  if (nrows > 0 && (st = check_required(f, "rows", rows))) return st;     // also to measure
+  if (nrows > 0 && (st = check_required(f, "part_ids", part_ids))) return st;
+  if ((st = check_aligned(f, 4, {{"part_ids", part_ids}}))) return st;
+  if ((st = check_required(f, "out_part_rows", out_part_rows))) return st;
+  if ((st = check_aligned(f, 8, {{"out_part_rows", out_part_rows}, {"out_indices", out_indices},
+                                 {"out_positions", out_positions}})))
+    return st;
   TakeArgs a;
-  int st = take_args(s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, f, &a);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
-  a.n = nrows;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_partition(a, part_ids, num_parts, out_part_rows, out_indices, out_positions, hs);
+  if ((st = take_args(f, s, rows, row_offsets, nrows, nrows, out_rows, out_capacity, out_offsets, &a)))
+    return st;
+  return launch_checked(hs, &a, [&] {
+    return launch_partition(a, part_ids, num_parts, out_part_rows, out_indices, out_positions, hs);
+  });
 }
 
 // Batches of one schema end to end (partition.hip): the vertical counterpart of fury_row_zip.
@@ -1405,56 +1439,35 @@ int fury_row_concat(const fury_schema* s, const fury_concat_source* sources, int
                     void* out_rows, int64_t out_capacity, int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_concat");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
-  if (!sources) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the source table is null");
+  int st = check_required(f, "schema", s);
+  if (st) return st;
+  if ((st = check_required(f, "the source table", sources))) return st;
   if (num_sources < 1 || num_sources > FURY_CONCAT_MAX_SOURCES)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": num_sources " + std::to_string(num_sources) + " is not in [1, " +
-                         std::to_string(FURY_CONCAT_MAX_SOURCES) + "]");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (misaligned(out_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets must be 8-byte aligned");
+    return invalid(f, "num_sources " + std::to_string(num_sources) + " is not in [1, " +
+                          std::to_string(FURY_CONCAT_MAX_SOURCES) + "]");
   ConcatArgs a{};
   for (int32_t k = 0; k < num_sources; k++) {
     const fury_concat_source& c = sources[k];
     const std::string src = f + ": source " + std::to_string(k);
-    if (c.nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": nrows < 0");
-    if (c.nrows > INT64_MAX - a.base[k]) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": batch too large");
+    if ((st = check_count(src, "nrows", c.nrows))) return st;
+    if (c.nrows > INT64_MAX - a.base[k]) return invalid(f, "batch too large");
     a.base[k + 1] = a.base[k] + c.nrows;
     if (c.nrows == 0) continue;       // an empty source is never read
-    if (!c.rows) return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows is null");
-    if (misaligned(c.rows, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows must be 8-byte aligned");
-    if (!s->is_fixed && !c.row_offsets)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": variable-length rows need row_offsets");
-    if (misaligned(c.row_offsets, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": row_offsets must be 8-byte aligned");
+    if ((st = check_source(src, c.rows, c.row_offsets, rows_of(s), true))) return st;
+    if ((st = check_aligned(src, 8, {{"row_offsets", c.row_offsets}}))) return st;
     a.rows[k] = static_cast<const uint8_t*>(c.rows);
     a.ro[k] = s->is_fixed ? nullptr : c.row_offsets;    // fixed schemas: row i at i * fixed_size
   }
-  const int64_t n = a.base[num_sources];
-  int st = too_large(n, s->fixed_size);
-  if (st) return set_error(st, f + ": batch too large");
-  if (!s->is_fixed && !out_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need out_offsets");
-  if (s->is_fixed && out_rows && s->fixed_size > 0 && out_capacity / s->fixed_size < n)
-    return set_error(FURY_ERR_CAPACITY,
-                     f + ": out_capacity " + std::to_string(out_capacity) + " < " + std::to_string(n) +
-                         " rows of " + std::to_string(s->fixed_size) + " bytes");
-  st = take_device_error(hs);
-  if (st) return st;
   a.nsrc = num_sources;
   a.fixed = s->is_fixed ? 1 : 0;
   a.fixed_size = s->fixed_size;
-  a.n = n;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_concat(a, hs);
+  a.n = a.base[num_sources];
+  if ((st = too_large(a.n, s->fixed_size))) return set_error(st, f + ": batch too large");
+  if ((st = check_aligned(f, 8, {{"out_offsets", out_offsets}}))) return st;
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a,
+                         s->is_fixed ? nullptr : kNeedOutOffsets, a.n, s->fixed_size)))
+    return st;
+  return launch_checked(hs, &a, [&] { return launch_concat(a, hs); });
 }
 
 // A subset of the fields, as rows (select.hip): BinaryRow's getters feeding a BinaryRowWriter of the
@@ -1466,38 +1479,24 @@ int fury_row_select(const fury_schema* s, const int32_t* fields, int32_t num_sel
   const std::string f("fury_row_select");
   int st = check_field_selection(s, fields, num_selected, f);
   if (st) return st;
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (misaligned(row_offsets, 8) || misaligned(out_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets / out_offsets must be 8-byte aligned");
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"out_offsets", out_offsets}}))) return st;
   Selection sel = make_selection(num_selected, 4, [&](int32_t) { return s; },
                                  [&](int32_t j) { return fields[j]; });
-  if (!s->is_fixed && !row_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": variable-length rows need row_offsets");
-  if (!sel.var.empty() && !out_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": a selection with a variable-length field needs out_offsets");
-  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  st = check_fixed_capacity(sel, out_rows, out_capacity, nrows, f);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
   SelectArgs a{};
+  if ((st = check_source(f, rows, row_offsets, rows_of(s), nrows > 0, &a))) return st;
+  // rows of a fixed-width selection sit at r * out_fixed: their capacity is checked before the launch
+  const char* need = "a selection with a variable-length field needs out_offsets";
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a, sel.var.empty() ? nullptr : need, nrows,
+                         sel.out_fixed)))
+    return st;
   finish_selection(&sel, num_selected, &a);
-  a.rows = static_cast<const uint8_t*>(rows);
-  a.row_offsets = s->is_fixed ? nullptr : row_offsets;    // fixed schemas: row i at i * fixed_size
   a.nrows = nrows;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
   a.bitmap_bytes = s->bitmap_bytes;
   a.fixed_size = s->fixed_size;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_select(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
+  return launch_checked(hs, &a, [&] {
+    return launch_select(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
+  });
 }
 
 // The fields of several batches joined row by row (zip.hip): fury_row_select with a source per pick.
@@ -1506,63 +1505,40 @@ int fury_row_zip(const fury_zip_source* sources, int32_t num_sources, const int3
                  int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_zip");
-  if (!sources) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the source table is null");
+  if (!sources) return invalid(f, "the source table is null");
   const fury_schema* schemas[FURY_ZIP_MAX_SOURCES] = {};
   for (int32_t s = 0; s < num_sources && s < FURY_ZIP_MAX_SOURCES; s++) schemas[s] = sources[s].schema;
   int st = check_zip_picks(schemas, num_sources, picks, num_picks, f);
   if (st) return st;
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (misaligned(out_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets must be 8-byte aligned");
+  if ((st = check_count(f, "nrows", nrows))) return st;
   Selection sel = make_selection(num_picks, 5, [&](int32_t j) { return schemas[picks[2 * j]]; },
                                  [&](int32_t j) { return picks[2 * j + 1]; });
-  uint32_t used = 0;
+  ZipArgs a{};
   for (int32_t j = 0; j < num_picks; j++) {
     sel.table[5 * static_cast<size_t>(j) + 4] = picks[2 * j];     // the source word
-    used |= 1u << picks[2 * j];
+    a.used |= 1u << picks[2 * j];
   }
   for (int32_t s = 0; s < num_sources; s++) {       // a source no pick names is never read
-    if (!((used >> s) & 1)) continue;
+    if (!((a.used >> s) & 1)) continue;
     const std::string src = f + ": source " + std::to_string(s);
-    if (misaligned(sources[s].rows, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows must be 8-byte aligned");
-    if (misaligned(sources[s].row_offsets, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": row_offsets must be 8-byte aligned");
-    if (!schemas[s]->is_fixed && !sources[s].row_offsets)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": variable-length rows need row_offsets");
-    if (nrows > 0 && !sources[s].rows)
-      return set_error(FURY_ERR_INVALID_ARGUMENT, src + ": rows is null");
-  }
-  if (sel.out_fixed > INT32_MAX - 7)
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": the zipped row header exceeds 2 GiB");
-  if (!sel.var.empty() && !out_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": picks with a variable-length field need out_offsets");
-  st = check_fixed_capacity(sel, out_rows, out_capacity, nrows, f);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
-  ZipArgs a{};
-  finish_selection(&sel, num_picks, &a);
-  for (int32_t s = 0; s < num_sources; s++) {
-    if (!((used >> s) & 1)) continue;
-    a.src[s].rows = static_cast<const uint8_t*>(sources[s].rows);
-    // fixed schemas: row i at i * fixed_size
-    a.src[s].row_offsets = schemas[s]->is_fixed ? nullptr : sources[s].row_offsets;
+    if ((st = check_aligned(src, 8, {{"row_offsets", sources[s].row_offsets}}))) return st;
+    if ((st = check_source(src, sources[s].rows, sources[s].row_offsets, rows_of(schemas[s]), nrows > 0,
+                           &a.src[s])))
+      return st;
     a.src[s].bitmap_bytes = schemas[s]->bitmap_bytes;
     a.src[s].fixed_size = schemas[s]->fixed_size;
   }
+  if (sel.out_fixed > INT32_MAX - 7) return invalid(f, "the zipped row header exceeds 2 GiB");
+  if ((st = check_aligned(f, 8, {{"out_offsets", out_offsets}}))) return st;
+  const char* need = "picks with a variable-length field need out_offsets";
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a, sel.var.empty() ? nullptr : need, nrows,
+                         sel.out_fixed)))
+    return st;
+  finish_selection(&sel, num_picks, &a);
   a.nrows = nrows;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
-  a.used = used;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_zip(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
+  return launch_checked(hs, &a, [&] {
+    return launch_zip(a, sel.table.data(), static_cast<int>(sel.table.size()), hs);
+  });
 }
 
 // Nested values as batches (extract.hip): getStruct / getArray / getMap over a batch.  The path is
@@ -1576,39 +1552,23 @@ int fury_row_extract(const fury_schema* s, const int32_t* path, int32_t path_len
   ExtractPath p;
   int st = resolve_extract_path(s, path, path_len, f, &p);
   if (st) return st;
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
-  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
-  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
-  if (misaligned(row_offsets, 8) || misaligned(out_offsets, 8) || misaligned(out_count, 8) ||
-      misaligned(out_indices, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": row_offsets / out_offsets / out_count / out_indices must be 8-byte aligned");
-  if (misaligned(out_validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_validity must be 4-byte aligned");
-  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  st = take_device_error(hs);
-  if (st) return st;
   ExtractArgs a{};
-  a.rows = static_cast<const uint8_t*>(rows);
-  a.row_offsets = row_offsets;
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if ((st = check_source(f, rows, row_offsets, kOffsetRows, nrows > 0, &a))) return st;
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a, kOutOffsetsNull))) return st;
+  if ((st = check_required(f, "out_count", out_count))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"out_offsets", out_offsets},
+                                 {"out_count", out_count}, {"out_indices", out_indices}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"out_validity", out_validity}}))) return st;
   a.nrows = nrows;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
   a.out_count = out_count;
   a.out_indices = out_indices;
   a.out_validity = reinterpret_cast<uint32_t*>(out_validity);
   set_path(&a, path_len, p.nfields, path);
   a.min_size = p.min_size;
   a.exact = p.exact;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_extract(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_extract(a, hs); });
 }
 
 // List and map elements as batches (explode.hip): BinaryArray.getStruct / getArray / getMap and
@@ -1625,46 +1585,31 @@ int fury_row_explode(const fury_schema* s, const int32_t* path, int32_t path_len
   ExplodePath p;
   int st = resolve_explode_path(s, path, path_len, side, f, &p);
   if (st) return st;
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
-  if (!out_list_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_list_offsets is null");
-  if (misaligned(row_offsets, 8) || misaligned(out_list_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": row_offsets / out_list_offsets must be 8-byte aligned");
-  if (misaligned(out_entry_validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_entry_validity must be 4-byte aligned");
-  if (!out_offsets) {                 // the count form
-    if (out_rows || out_count || out_parents || out_ordinals || out_validity)
-      return set_error(FURY_ERR_INVALID_ARGUMENT,
-                       f + ": out_offsets is null (the count form): out_rows, out_count, out_parents, "
-                           "out_ordinals and out_validity must be null too");
-  } else {
-    if (elem_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": elem_capacity < 0");
-    if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-    if (misaligned(out_rows, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-    if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
-    if (misaligned(out_offsets, 8) || misaligned(out_count, 8) || misaligned(out_parents, 8))
-      return set_error(FURY_ERR_INVALID_ARGUMENT,
-                       f + ": out_offsets / out_count / out_parents must be 8-byte aligned");
-    if (misaligned(out_ordinals, 4) || misaligned(out_validity, 4))
-      return set_error(FURY_ERR_INVALID_ARGUMENT,
-                       f + ": out_ordinals / out_validity must be 4-byte aligned");
-  }
-  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  st = take_device_error(hs);
-  if (st) return st;
   ExplodeArgs a{};
-  a.rows = static_cast<const uint8_t*>(rows);
-  a.row_offsets = row_offsets;
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if ((st = check_source(f, rows, row_offsets, kOffsetRows, nrows > 0, &a))) return st;
+  if ((st = check_required(f, "out_list_offsets", out_list_offsets))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"out_list_offsets", out_list_offsets}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"out_entry_validity", out_entry_validity}}))) return st;
+  if (!out_offsets) {                 // the count form: no output batch, `a` keeps its zeros
+    if (out_rows || out_count || out_parents || out_ordinals || out_validity)
+      return invalid(f, "out_offsets is null (the count form): out_rows, out_count, out_parents, "
+                        "out_ordinals and out_validity must be null too");
+  } else {
+    if ((st = check_count(f, "elem_capacity", elem_capacity))) return st;
+    if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a, kOutOffsetsNull))) return st;
+    if ((st = check_required(f, "out_count", out_count))) return st;
+    if ((st = check_aligned(f, 8, {{"out_offsets", out_offsets}, {"out_count", out_count},
+                                   {"out_parents", out_parents}})))
+      return st;
+    if ((st = check_aligned(f, 4, {{"out_ordinals", out_ordinals}, {"out_validity", out_validity}})))
+      return st;
+  }
   a.nrows = nrows;
   a.out_list_offsets = out_list_offsets;
   a.out_entry_validity = reinterpret_cast<uint32_t*>(out_entry_validity);
   a.elem_cap = out_offsets ? elem_capacity : 0;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
   a.out_count = out_count;
   a.out_parents = out_parents;
   a.out_ordinals = out_ordinals;
@@ -1676,36 +1621,27 @@ int fury_row_explode(const fury_schema* s, const int32_t* path, int32_t path_len
   a.side = side;
   a.elem_min = p.elem_min;
   a.elem_exact = p.elem_exact;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_explode(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_explode(a, hs); });
 }
 
 // The checks fury_row_implode and fury_row_wrap share, after their schema checks; fills what both set.
 static int implode_args(const OwnedField& value, const void* values, const int64_t* value_offsets,
                         int64_t num_values, int64_t nrows, void* out_rows, int64_t out_capacity,
                         int64_t* out_offsets, const std::string& f, ImplodeArgs* a) {
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (num_values < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_values < 0");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(values, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values must be 8-byte aligned");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (!value_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_offsets is null");
-  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
-  if (misaligned(value_offsets, 8) || misaligned(out_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": value_offsets / out_offsets must be 8-byte aligned");
-  if (num_values > 0 && !values) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values is null");
   *a = ImplodeArgs{};
+  int st = check_count(f, "nrows", nrows);
+  if (st) return st;
+  if ((st = check_count(f, "num_values", num_values))) return st;
+  if ((st = check_aligned(f, 8, {{"values", values}}))) return st;
+  if ((st = check_required(f, "value_offsets", value_offsets))) return st;
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, a, kOutOffsetsNull))) return st;
+  if ((st = check_aligned(f, 8, {{"value_offsets", value_offsets}, {"out_offsets", out_offsets}})))
+    return st;
+  if (num_values > 0 && (st = check_required(f, "values", values))) return st;
   a->values = static_cast<const uint8_t*>(values);
   a->value_offsets = value_offsets;
   a->num_values = num_values;
   a->nrows = nrows;
-  a->out = static_cast<uint8_t*>(out_rows);
-  a->cap = out_rows ? out_capacity : 0;
-  a->out_offsets = out_offsets;
   a->least = 8;                       // [int64 numElements] / [int64 keyArrayBytes]
   if (value.type_id == FURY_TYPE_STRUCT) {
     const int64_t m = static_cast<int64_t>(value.children.size());
@@ -1727,7 +1663,7 @@ int fury_row_implode(const fury_schema* s, const void* values, const int64_t* va
                      int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_implode");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (!s) return invalid(f, "schema is null");
   if (s->root == 0 && s->num_fields != 1)
     return set_error(FURY_ERR_UNSUPPORTED,
                      f + ": a row schema of " + std::to_string(s->num_fields) + " fields: the target "
@@ -1746,29 +1682,23 @@ int fury_row_implode(const fury_schema* s, const void* values, const int64_t* va
                      f + ": the elements of " + list.name + " are not STRUCT, LIST or MAP: such a list "
                          "encodes from a flat child column through fury_row_encode");
   if (s->root != 0 && entry_validity)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": entry_validity with a collection schema: an array entry is never null");
-  if (num_elements < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_elements < 0");
-  if (!list_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": list_offsets is null");
-  if (misaligned(list_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": list_offsets must be 8-byte aligned");
-  if (misaligned(entry_validity, 4) || misaligned(elem_validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": entry_validity / elem_validity must be 4-byte aligned");
+    return invalid(f, "entry_validity with a collection schema: an array entry is never null");
+  int st = check_count(f, "num_elements", num_elements);
+  if (st) return st;
+  if ((st = check_required(f, "list_offsets", list_offsets))) return st;
+  if ((st = check_aligned(f, 8, {{"list_offsets", list_offsets}}))) return st;
+  if ((st = check_aligned(f, 4, {{"entry_validity", entry_validity}, {"elem_validity", elem_validity}})))
+    return st;
   ImplodeArgs a;
-  int st = implode_args(elem, values, value_offsets, num_values, nrows, out_rows, out_capacity,
-                        out_offsets, f, &a);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
+  if ((st = implode_args(elem, values, value_offsets, num_values, nrows, out_rows, out_capacity,
+                         out_offsets, f, &a)))
+    return st;
   a.list_offsets = list_offsets;
   a.entry_validity = reinterpret_cast<const uint32_t*>(entry_validity);
   a.elem_validity = reinterpret_cast<const uint32_t*>(elem_validity);
   a.num_elements = num_elements;
   a.prefix = s->root == 0 ? 16 : 0;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_implode(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_implode(a, hs); });
 }
 
 // Nested values back into one-field rows (implode.hip): BinaryRowWriter.write(0, BinaryRow |
@@ -1778,7 +1708,7 @@ int fury_row_wrap(const fury_schema* s, const void* values, const int64_t* value
                   int64_t out_capacity, int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_wrap");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (!s) return invalid(f, "schema is null");
   if (s->root != 0)
     return set_error(FURY_ERR_UNSUPPORTED,
                      f + ": a collection schema: the target is a row schema with exactly one field");
@@ -1791,21 +1721,17 @@ int fury_row_wrap(const fury_schema* s, const void* values, const int64_t* value
   if (!is_nested(value.type_id))
     return set_error(FURY_ERR_UNSUPPORTED,
                      f + ": the target " + value.name + " is not a STRUCT, LIST or MAP");
-  if (misaligned(validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": validity must be 4-byte aligned");
+  int st = check_aligned(f, 4, {{"validity", validity}});
+  if (st) return st;
   ImplodeArgs a;
-  int st = implode_args(value, values, value_offsets, num_values, nrows, out_rows, out_capacity,
-                        out_offsets, f, &a);
-  if (st) return st;
-  st = take_device_error(hs);
-  if (st) return st;
+  if ((st = implode_args(value, values, value_offsets, num_values, nrows, out_rows, out_capacity,
+                         out_offsets, f, &a)))
+    return st;
   a.elem_validity = reinterpret_cast<const uint32_t*>(validity);
   a.num_elements = nrows;
   a.prefix = 16;
   a.wrap = 1;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_implode(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_implode(a, hs); });
 }
 
 // A map's key and value arrays as two batches (map.hip): BinaryMap.keyArray / valueArray over a batch.
@@ -1820,34 +1746,24 @@ int fury_row_map_split(const fury_schema* s, const int32_t* path, int32_t path_l
   MapPath p;
   int st = resolve_map_path(s, path, path_len, f, &p);
   if (st) return st;
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (key_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": key_capacity < 0");
-  if (value_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_capacity < 0");
-  if (misaligned(rows, 8)) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows must be 8-byte aligned");
-  if (misaligned(out_keys, 8) || misaligned(out_values, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_keys / out_values must be 8-byte aligned");
-  if (!row_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": row_offsets is null");
-  if (!out_key_offsets && !out_value_offsets)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": out_key_offsets and out_value_offsets are both null: no side is wanted");
-  if ((out_keys && !out_key_offsets) || (out_values && !out_value_offsets))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": out_keys / out_values without its offsets (a side whose offsets are null "
-                         "is skipped: its buffer must be null too)");
-  if (!out_count) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_count is null");
-  if (misaligned(row_offsets, 8) || misaligned(out_key_offsets, 8) || misaligned(out_value_offsets, 8) ||
-      misaligned(out_count, 8) || misaligned(out_indices, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": row_offsets / out_key_offsets / out_value_offsets / out_count / out_indices "
-                         "must be 8-byte aligned");
-  if (misaligned(out_validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_validity must be 4-byte aligned");
-  if (nrows > 0 && !rows) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": rows is null");
-  st = take_device_error(hs);
-  if (st) return st;
   MapSplitArgs a{};
-  a.rows = static_cast<const uint8_t*>(rows);
-  a.row_offsets = row_offsets;
+  if ((st = check_count(f, "nrows", nrows))) return st;
+  if ((st = check_count(f, "key_capacity", key_capacity))) return st;
+  if ((st = check_count(f, "value_capacity", value_capacity))) return st;
+  if ((st = check_source(f, rows, row_offsets, kOffsetRows, nrows > 0, &a))) return st;
+  // the two output batches: a side is wanted when its offsets are given
+  if ((st = check_aligned(f, 8, {{"out_keys", out_keys}, {"out_values", out_values}}))) return st;
+  if (!out_key_offsets && !out_value_offsets)
+    return invalid(f, "out_key_offsets and out_value_offsets are both null: no side is wanted");
+  if ((out_keys && !out_key_offsets) || (out_values && !out_value_offsets))
+    return invalid(f, "out_keys / out_values without its offsets (a side whose offsets are null "
+                      "is skipped: its buffer must be null too)");
+  if ((st = check_required(f, "out_count", out_count))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"out_key_offsets", out_key_offsets},
+                                 {"out_value_offsets", out_value_offsets}, {"out_count", out_count},
+                                 {"out_indices", out_indices}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"out_validity", out_validity}}))) return st;
   a.nrows = nrows;
   a.keys = MapSide{static_cast<uint8_t*>(out_keys), out_keys ? key_capacity : 0, out_key_offsets,
                    element_width(p.map->children[0].type_id)};
@@ -1859,9 +1775,7 @@ int fury_row_map_split(const fury_schema* s, const int32_t* path, int32_t path_l
   set_path(&a, s->root != 0 ? 0 : path_len, p.path.nfields, path);
   a.min_size = 8;
   a.exact = 0;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_map_split(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_map_split(a, hs); });
 }
 
 // Two array batches back into maps (map.hip): BinaryMap(keys, values, field) over a batch, inside a
@@ -1872,7 +1786,7 @@ int fury_row_map_join(const fury_schema* s, const void* keys, const int64_t* key
                       int64_t* out_offsets, void* stream) {
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const std::string f("fury_row_map_join");
-  if (!s) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": schema is null");
+  if (!s) return invalid(f, "schema is null");
   if (s->root == 0 && s->num_fields != 1)
     return set_error(FURY_ERR_UNSUPPORTED,
                      f + ": a row schema of " + std::to_string(s->num_fields) + " fields: the target "
@@ -1882,28 +1796,21 @@ int fury_row_map_join(const fury_schema* s, const void* keys, const int64_t* key
   if (map.type_id != FURY_TYPE_MAP)
     return set_error(FURY_ERR_UNSUPPORTED, f + ": the target " + map.name + " is not a MAP");
   if (s->root != 0 && validity)
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": validity with a collection schema: a map entry is never null");
-  if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": nrows < 0");
-  if (num_values < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": num_values < 0");
-  if (out_capacity < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_capacity < 0");
-  if (misaligned(keys, 8) || misaligned(values, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": keys / values must be 8-byte aligned");
-  if (misaligned(out_rows, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_rows must be 8-byte aligned");
-  if (!key_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": key_offsets is null");
-  if (!value_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": value_offsets is null");
-  if (!out_offsets) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": out_offsets is null");
-  if (misaligned(key_offsets, 8) || misaligned(value_offsets, 8) || misaligned(out_offsets, 8))
-    return set_error(FURY_ERR_INVALID_ARGUMENT,
-                     f + ": key_offsets / value_offsets / out_offsets must be 8-byte aligned");
-  if (misaligned(validity, 4))
-    return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": validity must be 4-byte aligned");
-  if (num_values > 0 && !keys) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": keys is null");
-  if (num_values > 0 && !values) return set_error(FURY_ERR_INVALID_ARGUMENT, f + ": values is null");
-  int st = take_device_error(hs);
-  if (st) return st;
+    return invalid(f, "validity with a collection schema: a map entry is never null");
   MapJoinArgs a{};
+  int st = check_count(f, "nrows", nrows);
+  if (st) return st;
+  if ((st = check_count(f, "num_values", num_values))) return st;
+  if ((st = check_aligned(f, 8, {{"keys", keys}, {"values", values}}))) return st;
+  if ((st = check_required(f, "key_offsets", key_offsets))) return st;
+  if ((st = check_required(f, "value_offsets", value_offsets))) return st;
+  if ((st = check_output(f, out_rows, out_capacity, out_offsets, &a, kOutOffsetsNull))) return st;
+  if ((st = check_aligned(f, 8, {{"key_offsets", key_offsets}, {"value_offsets", value_offsets},
+                                 {"out_offsets", out_offsets}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"validity", validity}}))) return st;
+  if (num_values > 0 && (st = check_required(f, "keys", keys))) return st;
+  if (num_values > 0 && (st = check_required(f, "values", values))) return st;
   a.keys = static_cast<const uint8_t*>(keys);
   a.key_offsets = key_offsets;
   a.values = static_cast<const uint8_t*>(values);
@@ -1911,13 +1818,8 @@ int fury_row_map_join(const fury_schema* s, const void* keys, const int64_t* key
   a.num_values = num_values;
   a.validity = reinterpret_cast<const uint32_t*>(validity);
   a.nrows = nrows;
-  a.out = static_cast<uint8_t*>(out_rows);
-  a.cap = out_rows ? out_capacity : 0;
-  a.out_offsets = out_offsets;
   a.prefix = s->root == 0 ? 16 : 0;
-  st = device_error_word(hs, &a.err);
-  if (st) return st;
-  return launch_map_join(a, hs);
+  return launch_checked(hs, &a, [&] { return launch_map_join(a, hs); });
 }
 
 int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* row_offsets,

@@ -336,6 +336,17 @@ class RowEncoder:
             rows.numel() * rows.element_size(), _stream_handle(stream)))
 
     # -- bound calls: the argument block built once, for hot loops --------------------------
+    def _bound(self, fn, args, keep: list, *alive):
+        """The callable every ``bind_*`` returns: it re-issues ``fn(*args)`` and raises on a
+        failure status, nothing else per call.  Its ``keep`` holds what ``args`` points into --
+        the ctypes objects in ``keep`` and the caller's buffers ``alive`` -- and this encoder with
+        its Schema: the schema handle in ``args`` lives as long as the Schema object, so a dropped
+        encoder would otherwise free it under the call."""
+        def call():
+            _check(fn(*args))
+        call.keep = (keep, *alive, self, self._schema)
+        return call
+
     def bind_encode(self, columns: Sequence[Column], nrows: int, rows: torch.Tensor,
                     row_offsets: Optional[torch.Tensor] = None, stream=None,
                     measured: bool = False):
@@ -355,13 +366,7 @@ class RowEncoder:
             args = (self._schema.handle, cc, nrows, _ptr(row_offsets), _ptr(rows),
                     _stream_handle(stream))
             fn = L.fury_row_encode
-
-        def call():
-            _check(fn(*args))
-        # the schema handle in args lives as long as the Schema object: keep it (and this
-        # encoder) alive with the callable, or a dropped encoder would free it under the call
-        call.keep = (keep, columns, rows, row_offsets, self, self._schema)
-        return call
+        return self._bound(fn, args, keep, columns, rows, row_offsets)
 
     def bind_decode(self, batch: RowBatch, cols: List[Column], stream=None, arrow: bool = False):
         """``decode_into`` bound like ``bind_encode``."""
@@ -370,11 +375,7 @@ class RowEncoder:
         fn = N.lib().fury_rows_to_arrow if arrow else N.lib().fury_row_decode
         args = (self._schema.handle, _ptr(batch.rows), _ptr(batch.row_offsets), batch.nrows, cc,
                 _stream_handle(stream))
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, cols, self, self._schema)
-        return call
+        return self._bound(fn, args, keep, batch, cols)
 
     def encode_batch(self, columns: Sequence[Column], nrows: int, stream=None) -> RowBatch:
         offs = self.measure(columns, nrows, stream)
@@ -383,7 +384,7 @@ class RowEncoder:
                 total = nrows * self._schema.fixed_size
             else:
                 total = int(offs[nrows].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            rows = self._row_buffer(total)
         self.encode_into(columns, nrows, rows, offs, stream)
         return RowBatch(rows[:total] if total else rows[:0], offs, nrows, self.schema_hash)
 
@@ -662,11 +663,7 @@ class RowEncoder:
         fn = N.lib().fury_row_project
         args = (self._schema.handle, sel, len(idx), _ptr(batch.rows), _ptr(batch.row_offsets),
                 batch.nrows, _c_columns(cols, keep), int(arrow), _stream_handle(stream))
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, sel, batch, cols, self, self._schema)
-        return call
+        return self._bound(fn, args, keep, sel, batch, cols)
 
     def project_batch(self, batch: RowBatch, select: Sequence, validity: bool = True, stream=None,
                       arrow: bool = False) -> List[Column]:
@@ -726,13 +723,8 @@ class RowEncoder:
                     row_mask: Optional[torch.Tensor] = None, stream=None):
         """``update_fields`` bound like ``bind_project``: descriptors and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_update
         args = self._update_args(batch, select, cols, row_mask, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, cols, row_mask, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_update, args, keep, batch, cols, row_mask)
 
     # -- row selection: whole rows gathered into a new batch (BinaryRow.copy() over a batch) -----
     def _check_hash(self, batch: RowBatch) -> None:
@@ -740,6 +732,55 @@ class RowEncoder:
             raise ClassNotCompatibleException(
                 f"Schema is not consistent, encoder schema is {self._schema}. self/peer schema "
                 f"hash are {self.schema_hash}/{batch.schema_hash}. Please check writer schema.")
+
+    def _fixed_size(self) -> Optional[int]:
+        """The row size of a fixed-width schema (row i at ``i * fixed_size``), else None."""
+        return self._schema.fixed_size if self._schema.is_fixed else None
+
+    def _row_buffer(self, total: int) -> torch.Tensor:
+        """A device buffer for ``total`` row bytes: never empty, so it always has an address."""
+        return torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+
+    def _measured(self, n: int, fixed_size: Optional[int], schema_hash: int, into,
+                  stream) -> RowBatch:
+        """The eager form of an ``*_into`` call, issued by ``into(out_rows, out_offsets)``, as a new
+        batch of ``n`` rows.  Output rows of ``fixed_size`` bytes know the size up front (no
+        offsets); ``None``: measure first with ``out_rows=None`` (one host read of the byte
+        total).  Then allocate, write, and ``device_status``."""
+        with _on(stream):
+            if fixed_size is not None:
+                offs = None
+                total = n * fixed_size
+            else:
+                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                into(None, offs)
+                total = int(offs[n].item())
+            rows = self._row_buffer(total)
+        into(rows, offs)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, n, schema_hash)
+
+    @staticmethod
+    def _counted(head: torch.Tensor, *ends: torch.Tensor):
+        """The count-and-total variant's one host read: ``head[0]`` is the entry count a measure
+        call wrote, ``ends`` are the one-entry tails of its offsets (the byte totals), gathered
+        behind it on the device.  Returns the ints ``(count, *totals)``."""
+        for k, end in enumerate(ends, 1):
+            head[k:k + 1] = end
+        return (int(x) for x in head.cpu())
+
+    def _take_kept(self, batch: RowBatch, idx: torch.Tensor, offs: Optional[torch.Tensor],
+                   count: int, total: int, stream):
+        """The second half of ``filter`` and ``partition``: the ``count`` rows ``idx[:count]`` a
+        measure call kept (``offs``: their offsets, None for a fixed-width schema; ``total``
+        bytes) copied into a new batch.  Returns ``(batch, idx[:count])``."""
+        with _on(stream):
+            rows = self._row_buffer(total)
+            kept = idx[:count]
+            offs = None if offs is None else offs[:count + 1]
+        self.take_into(batch, kept, rows, offs, stream)
+        self.device_status(stream)
+        return RowBatch(rows[:total], offs, count, self.schema_hash), kept
 
     def _indices(self, indices, stream) -> torch.Tensor:
         if not isinstance(indices, torch.Tensor):
@@ -775,32 +816,17 @@ class RowEncoder:
                   out_offsets: Optional[torch.Tensor] = None, stream=None):
         """``take_into`` bound like ``bind_update``: pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_take
         args = self._take_args(batch, indices, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_take, args, keep, batch, out_rows, out_offsets)
 
     def take(self, batch: RowBatch, indices, stream=None) -> RowBatch:
         """The rows ``indices`` of ``batch`` as a new batch.  Fixed-width schemas know the size up
         front; the others measure first (one host read of the byte total), then copy."""
         self._check_hash(batch)
         idx = self._indices(indices, stream)
-        n = idx.numel()
-        with _on(stream):
-            if self._schema.is_fixed:
-                offs = None
-                total = n * self._schema.fixed_size
-            else:
-                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-                self.take_into(batch, idx, None, offs, stream)
-                total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.take_into(batch, idx, rows, offs, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, self.schema_hash)
+        return self._measured(idx.numel(), self._fixed_size(), self.schema_hash,
+                              lambda rows, offs: self.take_into(batch, idx, rows, offs, stream),
+                              stream)
 
     def _mask_words(self, row_mask: torch.Tensor, nrows: int, stream) -> torch.Tensor:
         """``row_mask`` as the device bitmap the kernels read (LSB-first, whole 32-bit words): a
@@ -849,14 +875,8 @@ class RowEncoder:
                 count = int(head[0].item())
                 total = count * self._schema.fixed_size
             else:
-                head[1:] = offs[n:]
-                count, total = (int(x) for x in head.cpu())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-            kept = idx[:count]
-            offs = None if fixed else offs[:count + 1]
-        self.take_into(batch, kept, rows, offs, stream)
-        self.device_status(stream)
-        out = RowBatch(rows[:total], offs, count, self.schema_hash)
+                count, total = self._counted(head, offs[n:])
+        out, kept = self._take_kept(batch, idx, offs, count, total, stream)
         return (out, kept) if return_indices else out
 
     # -- rows by key, batches end to end (fury_row_partition / fury_row_concat) -------------------
@@ -921,15 +941,10 @@ class RowEncoder:
         """``partition_into`` bound like ``bind_take``: pointers resolved once (``part_ids`` is
         converted now; an int32 device tensor is read in place by every call)."""
         keep: list = []
-        fn = N.lib().fury_row_partition
         args = self._partition_args(batch, part_ids, num_parts, out_rows, out_offsets,
                                     out_part_rows, out_indices, out_positions, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_rows, out_offsets, out_part_rows, out_indices, out_positions,
-                     self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_partition, args, keep, batch, out_rows, out_offsets,
+                           out_part_rows, out_indices, out_positions)
 
     def partition(self, batch: RowBatch, part_ids, num_parts: int, stream=None,
                   return_indices: bool = False):
@@ -953,12 +968,7 @@ class RowEncoder:
                 total = count * self._schema.fixed_size
             else:
                 count, total = (int(x) for x in torch.stack((part_rows[num_parts], offs[n])).cpu())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-            kept = idx[:count]
-            offs = None if fixed else offs[:count + 1]
-        self.take_into(batch, kept, rows, offs, stream)
-        self.device_status(stream)
-        out = RowBatch(rows[:total], offs, count, self.schema_hash)
+        out, kept = self._take_kept(batch, idx, offs, count, total, stream)
         return (out, part_rows, kept) if return_indices else (out, part_rows)
 
     def slice_rows(self, batch: RowBatch, start: int, stop: int) -> RowBatch:
@@ -1005,19 +1015,9 @@ class RowEncoder:
         """``batches`` end to end as a new batch.  Fixed-width schemas know the size up front; the
         others measure first (one host read of the byte total), then copy."""
         batches = list(batches)
-        n = sum(b.nrows for b in batches)
-        with _on(stream):
-            if self._schema.is_fixed:
-                offs = None
-                total = n * self._schema.fixed_size
-            else:
-                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-                self.concat_into(batches, None, offs, stream)
-                total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.concat_into(batches, rows, offs, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, self.schema_hash)
+        return self._measured(sum(b.nrows for b in batches), self._fixed_size(), self.schema_hash,
+                              lambda rows, offs: self.concat_into(batches, rows, offs, stream),
+                              stream)
 
     # -- key hash: key fields of every row -> hash and partition id (fury_row_hash) ----------------
     def _hash_args(self, batch: RowBatch, keys: Sequence, out_hashes, out_part_ids, seed, num_parts,
@@ -1065,13 +1065,8 @@ class RowEncoder:
                   num_parts: Optional[int] = None, stream=None):
         """``hash_rows_into`` bound like ``bind_project``: keys and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_hash
         args = self._hash_args(batch, keys, out_hashes, out_part_ids, seed, num_parts, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_hashes, out_part_ids, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_hash, args, keep, batch, out_hashes, out_part_ids)
 
     def hash_rows(self, batch: RowBatch, keys: Sequence, seed: int = 0,
                   num_parts: Optional[int] = None, stream=None):
@@ -1146,13 +1141,8 @@ class RowEncoder:
                            out_offsets: Optional[torch.Tensor] = None, stream=None):
         """``select_fields_into`` bound like ``bind_take``: selection and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_select
         args = self._select_args(batch, select, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_select, args, keep, batch, out_rows, out_offsets)
 
     def select_fields(self, batch: RowBatch, select: Sequence, stream=None) -> RowBatch:
         """The fields ``select`` of every row of ``batch`` as a new batch of
@@ -1161,19 +1151,9 @@ class RowEncoder:
         self._check_hash(batch)
         idx = self._select(select)
         child = self.selected_encoder(idx)
-        n = batch.nrows
-        with _on(stream):
-            if child.schema().is_fixed:
-                offs = None
-                total = n * child.schema().fixed_size
-            else:
-                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-                self.select_fields_into(batch, idx, None, offs, stream)
-                total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.select_fields_into(batch, idx, rows, offs, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, child.schema_hash)
+        return self._measured(
+            batch.nrows, child._fixed_size(), child.schema_hash,
+            lambda rows, offs: self.select_fields_into(batch, idx, rows, offs, stream), stream)
 
     # -- zip: the fields of several batches joined row by row (several BinaryRows' getters feeding
     # one BinaryRowWriter).  ``self`` is source 0, ``others`` the (encoder, batch) pairs of sources
@@ -1271,13 +1251,8 @@ class RowEncoder:
                         out_offsets: Optional[torch.Tensor] = None, stream=None):
         """``zip_fields_into`` bound like ``bind_take``: picks and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_zip
         args = self._zip_args(batch, others, picks, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_zip, args, keep, batch, out_rows, out_offsets)
 
     def zip_fields(self, batch: RowBatch, others: Sequence, picks: Sequence,
                    stream=None) -> RowBatch:
@@ -1287,19 +1262,9 @@ class RowEncoder:
         encoders, _ = self._zip_sources(batch, others)
         idx = self._picks(encoders, picks)
         child = self.zipped_encoder(encoders[1:], idx)
-        n = batch.nrows
-        with _on(stream):
-            if child.schema().is_fixed:
-                offs = None
-                total = n * child.schema().fixed_size
-            else:
-                offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-                self.zip_fields_into(batch, others, idx, None, offs, stream)
-                total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.zip_fields_into(batch, others, idx, rows, offs, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, child.schema_hash)
+        return self._measured(
+            batch.nrows, child._fixed_size(), child.schema_hash,
+            lambda rows, offs: self.zip_fields_into(batch, others, idx, rows, offs, stream), stream)
 
     def _with_fields_picks(self, other_encoder: "RowEncoder") -> List[Tuple[int, int]]:
         """The picks of ``with_fields``: every field of this encoder in order, a field of
@@ -1394,15 +1359,10 @@ class RowEncoder:
                      out_validity: Optional[torch.Tensor] = None, stream=None):
         """``extract_into`` bound like ``bind_take``: path and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_extract
         args = self._extract_args(batch, path, out_rows, out_offsets, out_count, out_indices,
                                   out_validity, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_rows, out_offsets, out_count, out_indices, out_validity, self,
-                     self._schema)
-        return call
+        return self._bound(N.lib().fury_row_extract, args, keep, batch, out_rows, out_offsets,
+                           out_count, out_indices, out_validity)
 
     def extract(self, batch: RowBatch, path, stream=None, return_indices: bool = False):
         """``(values, validity)`` of the nested field ``path``: the non-null values as a new batch
@@ -1421,9 +1381,8 @@ class RowEncoder:
                    if return_indices else None)
             valid = torch.zeros(((n + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
             self.extract_into(batch, idx, None, offs, head[:1], None, None, stream)
-            head[1:] = offs[n:]
-            count, total = (int(x) for x in head.cpu())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            count, total = self._counted(head, offs[n:])
+            rows = self._row_buffer(total)
         self.extract_into(batch, idx, rows, offs, head[:1], src if n else None,
                           valid if n else None, stream)
         self.device_status(stream)
@@ -1518,16 +1477,12 @@ class RowEncoder:
                      elem_capacity: Optional[int] = None, stream=None):
         """``explode_into`` bound like ``bind_extract``: path and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_explode
         args = self._explode_args(batch, path, side, out_list_offsets, out_entry_validity, out_rows,
                                   out_offsets, out_count, out_parents, out_ordinals, out_validity,
                                   elem_capacity, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_list_offsets, out_entry_validity, out_rows, out_offsets,
-                     out_count, out_parents, out_ordinals, out_validity, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_explode, args, keep, batch, out_list_offsets,
+                           out_entry_validity, out_rows, out_offsets, out_count, out_parents,
+                           out_ordinals, out_validity)
 
     def explode(self, batch: RowBatch, path, side: str = "elements", stream=None):
         """``(elements, list_offsets, entry_validity, elem_validity, parents, ordinals)`` of the
@@ -1557,9 +1512,8 @@ class RowEncoder:
             valid = torch.zeros(((E + 31) // 32) * 4, dtype=torch.uint8, device=self.device)
             outs = (par if E else None, ords if E else None, valid if E else None)
             into(None, offs, head[:1], *outs)
-            head[1:] = offs[E:]
-            count, total = (int(x) for x in head.cpu())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            count, total = self._counted(head, offs[E:])
+            rows = self._row_buffer(total)
         into(rows, offs, head[:1], *outs)
         self.device_status(stream)
         out = RowBatch(rows[:total], offs[:count + 1], count, child.schema_hash)
@@ -1667,14 +1621,10 @@ class RowEncoder:
                      num_elements: Optional[int] = None, stream=None):
         """``implode_into`` bound like ``bind_explode``: pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_implode
         args = self._implode_args(elements, list_offsets, entry_validity, elem_validity,
                                   num_elements, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, elements, list_offsets, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_implode, args, keep, elements, list_offsets, out_rows,
+                           out_offsets)
 
     def implode(self, elements: RowBatch, list_offsets: torch.Tensor,
                 entry_validity: Optional[torch.Tensor] = None,
@@ -1685,18 +1635,10 @@ class RowEncoder:
         child = self._value_encoder(False)
         if child is not None:
             child._check_hash(elements)
-        n = list_offsets.numel() - 1
-        with _on(stream):
-            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            args = (elements, list_offsets)
-            kw = dict(entry_validity=entry_validity, elem_validity=elem_validity,
-                      num_elements=num_elements, stream=stream)
-            self.implode_into(*args, None, offs, **kw)
-            total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.implode_into(*args, rows, offs, **kw)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, self.schema_hash)
+        return self._measured(
+            list_offsets.numel() - 1, None, self.schema_hash,
+            lambda rows, offs: self.implode_into(elements, list_offsets, rows, offs, entry_validity,
+                                                 elem_validity, num_elements, stream), stream)
 
     def _wrap_args(self, values: RowBatch, validity, nrows, out_rows, out_offsets, stream,
                    keep: list):
@@ -1724,13 +1666,8 @@ class RowEncoder:
                   nrows: Optional[int] = None, stream=None):
         """``wrap_into`` bound like ``bind_extract``: pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_wrap
         args = self._wrap_args(values, validity, nrows, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, values, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_wrap, args, keep, values, out_rows, out_offsets)
 
     def wrap(self, values: RowBatch, validity: Optional[torch.Tensor] = None,
              nrows: Optional[int] = None, stream=None) -> RowBatch:
@@ -1738,14 +1675,9 @@ class RowEncoder:
         the byte total), then written."""
         keep: list = []
         n = self._wrap_args(values, validity, nrows, None, None, stream, keep)[5]
-        with _on(stream):
-            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            self.wrap_into(values, None, offs, validity, n, stream)
-            total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.wrap_into(values, rows, offs, validity, n, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, self.schema_hash)
+        return self._measured(
+            n, None, self.schema_hash,
+            lambda rows, offs: self.wrap_into(values, rows, offs, validity, n, stream), stream)
 
     def with_elements(self, batch: RowBatch, name, elements: RowBatch, list_offsets: torch.Tensor,
                       entry_validity: Optional[torch.Tensor] = None,
@@ -1834,16 +1766,11 @@ class RowEncoder:
                        out_validity: Optional[torch.Tensor] = None, stream=None):
         """``split_map_into`` bound like ``bind_extract``: path and pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_map_split
         args = self._split_map_args(batch, path, out_keys, out_key_offsets, out_values,
                                     out_value_offsets, out_count, out_indices, out_validity, stream,
                                     keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, batch, out_keys, out_key_offsets, out_values, out_value_offsets,
-                     out_count, out_indices, out_validity, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_map_split, args, keep, batch, out_keys, out_key_offsets,
+                           out_values, out_value_offsets, out_count, out_indices, out_validity)
 
     def split_map(self, batch: RowBatch, path, stream=None):
         """``(keys, values, indices, validity)`` of the MAP field ``path``: the key arrays and the
@@ -1863,11 +1790,9 @@ class RowEncoder:
             into = lambda k, v, *opt: RowEncoder.split_map_into(                 # noqa: E731
                 self, batch, idx, k, ko, v, vo, head[:1], *opt, stream=stream)
             into(None, None)
-            head[1:2] = ko[n:]
-            head[2:] = vo[n:]
-            count, kt, vt = (int(x) for x in head.cpu())
-            keys = torch.empty(max(kt, 16), dtype=torch.uint8, device=self.device)
-            vals = torch.empty(max(vt, 16), dtype=torch.uint8, device=self.device)
+            count, kt, vt = self._counted(head, ko[n:], vo[n:])
+            keys = self._row_buffer(kt)
+            vals = self._row_buffer(vt)
         into(keys, vals, src if n else None, valid if n else None)
         self.device_status(stream)
         return (RowBatch(keys[:kt], ko[:count + 1], count, 0),
@@ -1918,13 +1843,8 @@ class RowEncoder:
                       nrows: Optional[int] = None, stream=None):
         """``join_map_into`` bound like ``bind_wrap``: pointers resolved once."""
         keep: list = []
-        fn = N.lib().fury_row_map_join
         args = self._join_map_args(keys, values, validity, nrows, out_rows, out_offsets, stream, keep)
-
-        def call():
-            _check(fn(*args))
-        call.keep = (keep, keys, values, out_rows, out_offsets, self, self._schema)
-        return call
+        return self._bound(N.lib().fury_row_map_join, args, keep, keys, values, out_rows, out_offsets)
 
     def join_map(self, keys: RowBatch, values: RowBatch, validity: Optional[torch.Tensor] = None,
                  nrows: Optional[int] = None, stream=None) -> RowBatch:
@@ -1932,14 +1852,10 @@ class RowEncoder:
         of the byte total), then written."""
         keep: list = []
         n = self._join_map_args(keys, values, validity, nrows, None, None, stream, keep)[7]
-        with _on(stream):
-            offs = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-            self.join_map_into(keys, values, None, offs, validity, n, stream)
-            total = int(offs[n].item())
-            rows = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
-        self.join_map_into(keys, values, rows, offs, validity, n, stream)
-        self.device_status(stream)
-        return RowBatch(rows[:total], offs, n, self.schema_hash)
+        return self._measured(
+            n, None, self.schema_hash,
+            lambda rows, offs: self.join_map_into(keys, values, rows, offs, validity, n, stream),
+            stream)
 
     def with_map(self, batch: RowBatch, name, keys: RowBatch, values: RowBatch,
                  validity: Optional[torch.Tensor] = None, stream=None):
@@ -2052,7 +1968,7 @@ class RowEncoder:
         n = batch.nrows
         total = batch.rows.numel() + 12 * n
         with _on(stream):
-            out = torch.empty(max(total, 16), dtype=torch.uint8, device=self.device)
+            out = self._row_buffer(total)
             fo = torch.empty(n + 1, dtype=torch.int64, device=self.device)
         _check(N.lib().fury_frame_rows(self._schema.handle, _ptr(batch.rows),
                                        _ptr(batch.row_offsets), n, _ptr(out), _ptr(fo),
@@ -2063,8 +1979,7 @@ class RowEncoder:
         """Parses a ``decode(MemoryBuffer)`` stream; raises ClassNotCompatibleException on a
         schema-hash mismatch."""
         with _on(stream):
-            rows = torch.empty(max(stream_bytes.numel(), 16), dtype=torch.uint8,
-                               device=self.device)
+            rows = self._row_buffer(stream_bytes.numel())
             offs = torch.empty(nrows + 1, dtype=torch.int64, device=self.device)
         _check(N.lib().fury_unframe_rows(self._schema.handle, _ptr(stream_bytes),
                                          stream_bytes.numel(), nrows, _ptr(rows), _ptr(offs),

@@ -122,6 +122,24 @@ def test_column_mask_and_rows_checks(L, schemas):
     assert "row_offsets" in N.last_error()
 
 
+def test_rows_messages_name_the_function(L, schemas):
+    """The three checks of the row batch itself report like every other check of the call: the
+    message starts with the function's name."""
+    from fury_amd import _native as N
+    raw, rows = _buf()
+    raw2, vals = _buf()
+    up = L.fury_row_update
+    nar = schemas["narrow"].handle                   # variable-length rows
+    sel, m = _sel({f.name: i for i, f in enumerate(SCHEMAS["narrow"])}["d_int"])
+    c = _cols(N, 1, vals)
+    assert up(nar, sel, m, None, rows, 4, c, None, None) == INVALID
+    assert N.last_error() == "fury_row_update: rows is null"
+    assert up(nar, sel, m, rows + 4, rows, 4, c, None, None) == INVALID
+    assert N.last_error() == "fury_row_update: rows must be 8-byte aligned"
+    assert up(nar, sel, m, rows, None, 4, c, None, None) == INVALID
+    assert N.last_error() == "fury_row_update: variable-length rows need row_offsets"
+
+
 def test_unsupported_selections(L, schemas):
     from fury_amd import _native as N
     raw, rows = _buf()
