@@ -285,10 +285,12 @@ __global__ __launch_bounds__(kTakeThreads) void zip_write(ZipArgs a, const uint6
     store_words(a.out, a0, b0, [&](int64_t d) -> uint64_t {
       const int lo = staged_row(sh.oo, kn, d);      // every row has bytes
       const int64_t r = r0 + lo;
-      const int x = static_cast<int>(d - sh.oo[lo]);
+      // 64-bit until it is used: narrowed here, the compiler split the narrowing over the
+      // subtraction and a row that starts below 2^31 and ends above it read 2^32 bytes low
+      const int64_t x = d - sh.oo[lo];
       if (x < a.out_bitmap_bytes) return gl(wbm)[r * nbw + (x >> 3)];
       if (x < a.out_fixed_size) {
-        const int j = (x - a.out_bitmap_bytes) >> 3;
+        const int j = static_cast<int>((x - a.out_bitmap_bytes) >> 3);
         if ((gl(wbm)[r * nbw + (j >> 6)] >> (j & 63)) & 1) return 0;
         const int32_t width = T[5 * j + 1];
         const int s = T[5 * j + 4];

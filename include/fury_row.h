@@ -202,7 +202,14 @@ int fury_schema_get_info(const fury_schema* schema, fury_schema_info* info);
 /* ---- device batch codec ---------------------------------------------------------------- */
 /* Row sizes and their exclusive scan: row_offsets[0..nrows] (int64, device); row i occupies
  * [row_offsets[i], row_offsets[i+1]) and row_offsets[nrows] is the batch's byte total.
- * For is_fixed schemas this is optional (rows sit at i * fixed_size). */
+ * For is_fixed schemas this is optional (rows sit at i * fixed_size).
+ *
+ * Everywhere a function below takes `rows` with `row_offsets`, row_offsets[0] need not be 0: a batch
+ * may sit anywhere in its buffer (an interior slice of a larger batch with its offsets as they are, a
+ * batch encoded at row_offsets = measured + B), at byte positions past 2^31 and 2^32 alike, and every
+ * bounds rule reads "inside [0, row_offsets[nrows])" -- the lower bound is the buffer's byte 0, not
+ * row_offsets[0].  The one exception is fury_frame_rows, which places frame i at
+ * row_offsets[i] + 12 * i and so is defined for batches whose offsets start at 0. */
 int fury_row_measure(const fury_schema* schema, const fury_column* columns, int64_t nrows,
                      int64_t* row_offsets, void* stream);
 /* Encode nrows rows into `rows` (device, 8-byte aligned, row_offsets[nrows] bytes, or

@@ -516,3 +516,23 @@ def test_foreign_schema_hash(dev):
     foreign = RowBatch(b.rows, b.row_offsets, b.nrows, b.schema_hash + 1)
     with pytest.raises(ClassNotCompatibleException, match="Schema is not consistent"):
         src.enc.select_fields(foreign, ["f5"])
+
+
+def test_output_row_across_2g(dev):
+    """Regression (found by tests/test_high_offsets_gpu.py::test_dense_select_zip): select_write
+    narrowed a word's position in its row to 32 bits before the payload arithmetic, and for the
+    second word of every 16-byte chunk of the one output row that starts below byte 2^31 and ends
+    above it the source position came out 2^32 too low.  40 rows of 64 and 48 MiB in turn: row 36
+    is that row."""
+    import gc
+    from tests.test_high_offsets_gpu import across_2g, check_across_2g
+    enc, src, order, big, _ = across_2g(dev)
+    try:
+        def write(rows, offs):
+            enc.select_fields_into(big, ["a"], rows, offs)
+            enc.device_status()
+        check_across_2g(dev, enc.select_fields(src, ["a"]), order, write)
+    finally:
+        del big, _
+        gc.collect()
+        torch.cuda.empty_cache()

@@ -501,3 +501,23 @@ def test_foreign_schema_hash_and_row_counts(dev):
         a.enc.zip_fields(ba, [(b.enc, RowBatch(bb.rows, None, 65, b.enc.schema_hash + 1))], [(1, 0)])
     with pytest.raises(IllegalArgumentException, match="source 1 has 64 rows"):
         a.enc.zip_fields(ba, [(b.enc, RowBatch(bb.rows, None, 64, b.enc.schema_hash))], [(1, 0)])
+
+
+def test_output_row_across_2g(dev):
+    """Regression (found by tests/test_high_offsets_gpu.py::test_dense_select_zip): zip_write shared
+    select_write's 32-bit narrowing of a word's position in its row, which sent the second word of
+    every 16-byte chunk of the output row across byte 2^31 to a source position 2^32 too low.  Two
+    sources over the same 40 rows of 64 and 48 MiB in turn: row 36 is that row."""
+    import gc
+    from tests.test_high_offsets_gpu import across_2g, check_across_2g
+    enc, src, order, big, _ = across_2g(dev)
+    picks = [(1, "id"), (0, "a")]
+    try:
+        def write(rows, offs):
+            enc.zip_fields_into(big, [(enc, big)], picks, rows, offs)
+            enc.device_status()
+        check_across_2g(dev, enc.zip_fields(src, [(enc, src)], picks), order, write)
+    finally:
+        del big, _
+        gc.collect()
+        torch.cuda.empty_cache()
