@@ -444,6 +444,11 @@ void dev_free(void* p, hipStream_t stream) {
   g_cache_bytes += cls;
 }
 
+int64_t dev_live_blocks() {
+  std::lock_guard<std::mutex> lock(g_cache_mu);
+  return static_cast<int64_t>(g_cache_live.size());
+}
+
 DeviceTable::~DeviceTable() {
   if (dev) dev_free(dev, stream);
 }
@@ -1827,14 +1832,35 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
                         fury_decode_plan** plan, void* stream) {
   if (!s || !plan) return set_error(FURY_ERR_INVALID_ARGUMENT, "fury_decode_prepare: null argument");
   *plan = nullptr;
+  std::unique_ptr<fury_decode_plan> p(new fury_decode_plan());
+  const int st = decode_prepare(p.get(), s, rows, row_offsets, nrows, node_entries, node_bytes,
+                                static_cast<hipStream_t>(stream));
+  if (!st) *plan = p.release();
+  return st;
+}
+
+}  // extern "C"
+
+fury_decode_plan::~fury_decode_plan() {
+  lv.reset();
+  tree.reset();
+  wide.reset();
+  owned.reset();
+  if (owned_stream) {
+    release_error_slot(owned_stream);
+    (void)hipStreamDestroy(owned_stream);
+  }
+}
+
+int fury::decode_prepare(fury_decode_plan* p, const fury_schema* s, const void* rows,
+                         const int64_t* row_offsets, int64_t nrows, int64_t* node_entries,
+                         int64_t* node_bytes, hipStream_t hs) {
   if (nrows < 0) return set_error(FURY_ERR_INVALID_ARGUMENT, "nrows < 0");
   if (!s->device_ok) return set_error(FURY_ERR_UNSUPPORTED, "no device kernel for " + s->device_reason);
   if (nrows > 0 && (!rows || !row_offsets))
     return set_error(FURY_ERR_INVALID_ARGUMENT, "rows / row_offsets is null");
-  hipStream_t hs = static_cast<hipStream_t>(stream);
   if (const int e = take_device_error(hs)) return e;
   const int nn = static_cast<int>(s->nodes.size());
-  fury_decode_plan* p = new fury_decode_plan();
   p->schema = s;
   p->rows = static_cast<const uint8_t*>(rows);
   p->offs = row_offsets;
@@ -1845,15 +1871,12 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
   const bool wide_shape = nrows > 0 && !s->generic && !s->is_fixed && s->num_fields > 16 /* kRegCols: the register-staged kernels below */ &&
                           s->num_fields <= kMaxWideVarCols && knob::var_wide.load();
   int engine = knob::wide_engine.load();   // tuning.cpp: 0 auto, 1 the wide tiles, 2 the row walk
+  int64_t bytes = -1;                      // the batch's bytes, row_offsets[nrows]: not read yet
   if (wide_shape && engine == 0) {
-    int64_t bytes = 0;
     int st = check_hip(hipMemcpyAsync(&bytes, row_offsets + nrows, 8, hipMemcpyDeviceToHost, hs),
                        "hipMemcpyAsync batch bytes");
     if (!st) st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize");
-    if (st) {
-      delete p;
-      return st;
-    }
+    if (st) return st;
     engine = bytes > static_cast<int64_t>(knob::wide_walk_row.load()) * nrows ? 2 : 1;
   }
   const bool wide = wide_shape && engine != 2;
@@ -1863,15 +1886,11 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
     std::vector<int64_t> seq;
     int st = var_args(s, nullptr, nrows, true, false, &a, &dt, hs, true);
     if (!st) {
-      p->wide = new WidePlan();
-      st = wide_prepare(a, p->rows, row_offsets, hs, p->wide, &seq);
+      p->wide.reset(new WidePlan());
+      st = wide_prepare(a, p->rows, row_offsets, hs, bytes, p->wide.get(), &seq);
     }
     if (!st) st = take_device_error(hs);
-    if (st) {
-      if (p->wide) wide_free(p->wide);
-      delete p;
-      return st;
-    }
+    if (st) return st;
     int q = 0;
     for (int k = 0; k < s->num_fields; k++) {
       totals[2 * k] = nrows;
@@ -1884,13 +1903,17 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
   } else if (nrows > 0) {
     // both engines synchronise `stream`: rows whose values leave the batch are reported here.
     // The tile-staged engine first; the level engine when it declines the batch.
-    int st = tree_prepare(s, p->rows, row_offsets, nrows, hs, &p->tree, &totals);
-    if (!st && !p->tree) {
+    TreePlan* tree = nullptr;
+    int st = tree_prepare(s, p->rows, row_offsets, nrows, bytes, hs, &tree, &totals);
+    p->tree.reset(tree);
+    if (!st && !tree) {
       if (const int e = take_device_error(hs)) {
         st = e;
       } else {
         totals.assign(2 * nn, 0);
-        st = lv_prepare(s, p->rows, row_offsets, nrows, hs, &p->lv, &totals);
+        LvPlan* lv = nullptr;
+        st = lv_prepare(s, p->rows, row_offsets, nrows, hs, &lv, &totals);
+        p->lv.reset(lv);
       }
     }
     if (!st) {
@@ -1902,21 +1925,17 @@ int fury_decode_prepare(const fury_schema* s, const void* rows, const int64_t* r
       const int e = take_device_error(hs);
       if (e && st != FURY_ERR_DEVICE) st = e;
     }
-    if (st) {
-      if (p->lv) lv_free(p->lv);
-      if (p->tree) tree_free(p->tree);
-      delete p;
-      return st;
-    }
+    if (st) return st;
   }
   for (int i = 0; i < nn; i++) {
     if (node_entries) node_entries[i] = totals[2 * i];
     if (node_bytes) node_bytes[i] = totals[2 * i + 1];
   }
   p->totals = totals;
-  *plan = p;
   return FURY_OK;
 }
+
+extern "C" {
 
 int fury_decode_execute(fury_decode_plan* p, fury_column* cols, int32_t arrow, void* stream) {
   if (!p) return set_error(FURY_ERR_INVALID_ARGUMENT, "fury_decode_execute: plan is null");
@@ -1940,22 +1959,11 @@ int fury_decode_execute(fury_decode_plan* p, fury_column* cols, int32_t arrow, v
     if (st) return st;
     return wide_execute(a, p->rows, p->offs, hs, *p->wide);
   }
-  if (p->tree) return tree_execute(p->tree, outs, p->rows, p->offs, p->totals, hs);
-  return lv_execute(p->lv, outs, p->rows, p->offs, hs);
+  if (p->tree) return tree_execute(p->tree.get(), outs, p->rows, p->offs, p->totals, hs);
+  return lv_execute(p->lv.get(), outs, p->rows, p->offs, hs);
 }
 
-void fury_decode_plan_destroy(fury_decode_plan* p) {
-  if (!p) return;
-  if (p->lv) lv_free(p->lv);
-  if (p->tree) tree_free(p->tree);
-  if (p->wide) wide_free(p->wide);
-  if (p->owned) dev_free(p->owned, static_cast<hipStream_t>(p->owned_stream));
-  if (p->owned_stream) {
-    release_error_slot(static_cast<hipStream_t>(p->owned_stream));
-    (void)hipStreamDestroy(static_cast<hipStream_t>(p->owned_stream));
-  }
-  delete p;
-}
+void fury_decode_plan_destroy(fury_decode_plan* p) { delete p; }
 
 int fury_trim_workspace(int32_t device) {
   int n = 0;

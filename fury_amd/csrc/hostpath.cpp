@@ -858,24 +858,22 @@ int fury_decode_host_prepare(const fury_schema* s, const void* rows, const int64
   if (!s->device_ok) return set_error(FURY_ERR_UNSUPPORTED, "no device kernel for " + s->device_reason);
   int st = check_hip(hipSetDevice(device), "hipSetDevice");
   if (st) return st;
-  hipStream_t hs = nullptr;
-  if ((st = check_hip(hipStreamCreateWithFlags(&hs, hipStreamNonBlocking), "hipStreamCreate")))
+  // the plan owns the stream and the staged rows from here on: an error exit gives them back
+  std::unique_ptr<fury_decode_plan> p(new fury_decode_plan());
+  if ((st = check_hip(hipStreamCreateWithFlags(&p->owned_stream, hipStreamNonBlocking), "hipStreamCreate")))
     return st;
+  hipStream_t hs = p->owned_stream;
+  p->device = device;
   const int64_t total = nrows == 0 ? 0 : s->is_fixed && !row_offsets ? nrows * s->fixed_size
                                                                       : row_offsets[nrows];
   // The rows are staged in HBM even when pinned: the decode walks read them twice (prepare and
   // execute) in dependent chains, which over PCIe ran at 7 GB/s (1M nested rows, kernels on the
   // pinned rows) against one DMA copy here; the execute writes its outputs in place instead.
   // stage the rows and their offsets (fixed-width rows: offsets i * fixed_size) in HBM
-  uint8_t* d = nullptr;
   const int64_t rb = (total + 255) & ~int64_t(255);
   keep_pool(device);
-  st = dev_alloc(rb + (nrows + 1) * 8 + 16, hs, reinterpret_cast<void**>(&d));
-  if (st) {
-    release_error_slot(hs);
-    (void)hipStreamDestroy(hs);
-    return st;
-  }
+  if ((st = p->owned.alloc(rb + (nrows + 1) * 8 + 16, hs))) return st;
+  uint8_t* d = p->owned.as<uint8_t>();
   int64_t* doffs = reinterpret_cast<int64_t*>(d + rb);
   if (total > 0) (void)hipMemcpyAsync(d, rows, total, hipMemcpyHostToDevice, hs);
   if (nrows > 0) {
@@ -885,27 +883,12 @@ int fury_decode_host_prepare(const fury_schema* s, const void* rows, const int64
       std::vector<int64_t> o(nrows + 1);
       for (int64_t i = 0; i <= nrows; i++) o[i] = i * s->fixed_size;
       (void)hipMemcpyAsync(doffs, o.data(), (nrows + 1) * 8, hipMemcpyHostToDevice, hs);
-      if ((st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize"))) {
-        dev_free(d, hs);
-        release_error_slot(hs);
-        (void)hipStreamDestroy(hs);
-        return st;
-      }
+      if ((st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize"))) return st;
     }
   }
-  fury_decode_plan* p = nullptr;
-  st = fury_decode_prepare(s, d, doffs, nrows, node_entries, node_bytes, &p, hs);
-  if (st) {
-    dev_free(d, hs);
-    release_error_slot(hs);
-    (void)hipStreamDestroy(hs);
-    return st;
-  }
-  p->owned = d;
-  p->owned_stream = hs;
-  p->device = device;
-  *plan = p;
-  return FURY_OK;
+  st = decode_prepare(p.get(), s, d, doffs, nrows, node_entries, node_bytes, hs);
+  if (!st) *plan = p.release();
+  return st;
 }
 
 int fury_decode_host_execute(fury_decode_plan* p, fury_column* host) {
@@ -916,7 +899,7 @@ int fury_decode_host_execute(fury_decode_plan* p, fury_column* host) {
   if (s->num_fields > 0 && !host) return set_error(FURY_ERR_INVALID_ARGUMENT, "columns is null");
   int st = check_hip(hipSetDevice(p->device), "hipSetDevice");
   if (st) return st;
-  hipStream_t hs = static_cast<hipStream_t>(p->owned_stream);
+  hipStream_t hs = p->owned_stream;
   const int nn = static_cast<int>(s->nodes.size());
   // the host column tree in node (breadth-first) order
   std::vector<const fury_column*> hc(nn, nullptr);

@@ -65,23 +65,7 @@ struct fury_schema {
   std::vector<fury::GenTpl> nodes;
 };
 
-// Decode plan of the two-step (nested) decode, device and host-memory flavours.
-namespace fury { struct LvPlan; struct TreePlan; struct WidePlan; }
-
-struct fury_decode_plan {
-  const fury_schema* schema = nullptr;
-  const uint8_t* rows = nullptr;
-  const int64_t* offs = nullptr;
-  int64_t nrows = 0;
-  fury::LvPlan* lv = nullptr;      // level-by-level engine state (levels.hip); NULL when nrows = 0
-  fury::TreePlan* tree = nullptr;  // tile-staged engine state (tree.hip): used when set
-  fury::WidePlan* wide = nullptr;  // flat schemas of 17-256 fields (wide.hip): used when set
-  bool arrow = false;
-  std::vector<int64_t> totals;     // per node: Arrow entries, payload bytes
-  void* owned = nullptr;           // host flavour: the staged rows + offsets (device memory)
-  void* owned_stream = nullptr;    // host flavour: its stream
-  int32_t device = 0;
-};
+// struct fury_decode_plan is defined at the end of kernels.h (it owns device blocks: HIP types).
 
 namespace fury {
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "internal.h"
@@ -141,6 +142,36 @@ int64_t budget_errors();
 // their per-call host cost.
 int dev_alloc(int64_t bytes, hipStream_t stream, void** out);
 void dev_free(void* p, hipStream_t stream);
+int64_t dev_live_blocks();           // blocks handed out and not yet given back (tuning "workspace_live")
+// One cached block and the stream it goes back on when the holder goes (move-only).
+struct DevBlock {
+  void* p = nullptr;
+  hipStream_t stream = nullptr;
+  DevBlock() = default;
+  DevBlock(DevBlock&& o) noexcept : p(o.release()), stream(o.stream) {}
+  DevBlock& operator=(DevBlock&& o) noexcept {
+    if (this != &o) {
+      reset();
+      stream = o.stream;
+      p = o.release();
+    }
+    return *this;
+  }
+  ~DevBlock() { reset(); }
+  int alloc(int64_t bytes, hipStream_t s) {      // gives back the block it held
+    reset();
+    stream = s;
+    return dev_alloc(bytes, s, &p);
+  }
+  void reset() { dev_free(release(), stream); }
+  void* release() {
+    void* q = p;
+    p = nullptr;
+    return q;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+};
 
 // Decode bounds (round 3).  Every byte a decode reads lies in [0, total) of the rows buffer, total
 // = the batch's row bytes (row_offsets[nrows]): the reference's getters read through MemoryBuffer,
@@ -201,20 +232,26 @@ int workspace_reserve(size_t bytes, void** out);
 int encode_tile_rows(const VarArgs& a);
 int64_t lookback_timeouts();
 int var_dec_rows_rejected();          // forced "var_dec_rows" tiles whose images did not fit (plan used)
-// offsets_only: fury_row_decode_measure (the Arrow offsets of the variable-length fields only)
+// The wide decode's launch geometry: threads per tile, the LDS stage (~64 rows of the estimated row
+// size) and the per-wave images, tiles, sequence (STRING / BINARY / LIST) fields.
+struct WideGeom {
+  int nseq = 0, th = 256;
+  uint32_t stage = 0, imgs = 0;
+  int64_t nt = 0;
+};
 // Plan form of the wide decode (fury_decode_prepare / _execute): the count pass + scan once, the
 // per-tile bases kept for the write pass.
 struct WidePlan {
-  int64_t* ws = nullptr;
-  int64_t nt = 0;
-  int nseq = 0;
-  hipStream_t stream = nullptr;
+  DevBlock ws;               // the scanned per-tile bases
+  WideGeom g;                // what the prepare launched with; the execute's too, but for the stage
 };
+// batch_bytes: offs[nrows] where the caller has read it, -1: read here (one host sync)
 int wide_prepare(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
-                 WidePlan* wp, std::vector<int64_t>* seq_totals);
+                 int64_t batch_bytes, WidePlan* wp, std::vector<int64_t>* seq_totals);
 int wide_execute(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
                  const WidePlan& wp);
 void wide_free(WidePlan* wp);
+// offsets_only: fury_row_decode_measure (the Arrow offsets of the variable-length fields only)
 int launch_decode_wide(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
                        bool offsets_only);
 int launch_encode_wide(const VarArgs& a, const int64_t* offs, uint8_t* rows, int64_t cap,
@@ -665,11 +702,14 @@ int lv_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, i
 int lv_execute(const LvPlan* p, const GenNode* outs, const uint8_t* rows, const int64_t* offs,
                hipStream_t hs);
 void lv_free(LvPlan* p);
+// The pinned landing buffer of a prepare's totals (n words or more): one per host thread, kept.
+int64_t* pinned_totals(size_t n);
 // Row-walk nested decode (tree.hip / walk.hip): prepare = pass 1 + tile scan + one host sync (*out NULL:
 // the batch needs the level engine above), execute = pass 2 into gen_args' node table.
 struct TreePlan;
+// batch_bytes: offs[nrows] where the caller has read it, -1 otherwise.
 int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, int64_t nrows,
-                 hipStream_t hs, TreePlan** out, std::vector<int64_t>* totals);
+                 int64_t batch_bytes, hipStream_t hs, TreePlan** out, std::vector<int64_t>* totals);
 int tree_execute(const TreePlan* p, const GenNode* outs, const uint8_t* rows, const int64_t* offs,
                  const std::vector<int64_t>& totals, hipStream_t hs);
 void tree_free(TreePlan* p);
@@ -697,4 +737,31 @@ int ipc_schema_message(const fury_schema* s, std::vector<uint8_t>* out);
 int ipc_record_batch(const fury_schema* s, const fury_column* cols, int64_t n, uint8_t* out,
                      int64_t cap, int64_t* len, hipStream_t stream);
 
+// fury_decode_prepare into a plan the caller has made (capi.cpp): the host flavour's plan already
+// owns its stream and staged rows.
+int decode_prepare(fury_decode_plan* p, const fury_schema* s, const void* rows,
+                   const int64_t* row_offsets, int64_t nrows, int64_t* node_entries,
+                   int64_t* node_bytes, hipStream_t hs);
+
 }  // namespace fury
+
+// Decode plan of the two-step (nested) decode, device and host-memory flavours.  It owns its
+// parts; the destructor (capi.cpp) gives them back in this order: the engine state, the staged
+// rows, the private stream's error slot and the stream.
+struct fury_decode_plan {
+  template <class T>
+  using EnginePtr = std::unique_ptr<T, void (*)(T*)>;
+  const fury_schema* schema = nullptr;
+  const uint8_t* rows = nullptr;
+  const int64_t* offs = nullptr;
+  int64_t nrows = 0;
+  // at most one engine state is set; none when nrows = 0
+  EnginePtr<fury::LvPlan> lv{nullptr, fury::lv_free};        // level-by-level engine (levels.hip)
+  EnginePtr<fury::TreePlan> tree{nullptr, fury::tree_free};  // row walk / tile BFS (tree.hip)
+  EnginePtr<fury::WidePlan> wide{nullptr, fury::wide_free};  // flat schemas of 17-256 fields (wide.hip)
+  std::vector<int64_t> totals;     // per node: Arrow entries, payload bytes
+  fury::DevBlock owned;            // host flavour: the staged rows + offsets
+  hipStream_t owned_stream = nullptr;  // host flavour: its stream
+  int32_t device = 0;
+  ~fury_decode_plan();
+};

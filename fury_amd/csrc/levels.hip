@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -58,7 +59,7 @@ struct LvNode {
 struct LvPlan {
   std::vector<LvNode> nodes;        // device pointers (src, start) and entry counts
   int64_t nrows = 0;
-  std::vector<void*> bufs;          // stream-pool allocations owned by the plan
+  std::vector<DevBlock> bufs;       // what the nodes' src / start point into
   hipStream_t stream = nullptr;     // the stream they were allocated on (freed on it)
   int32_t ntop = 0;
   int32_t root = 0;
@@ -679,15 +680,17 @@ int launch_split(const LvPlan& p, const std::vector<int32_t>& list, const uint8_
 }
 
 int pool_alloc(LvPlan* p, int64_t bytes, void** out) {
-  *out = nullptr;
-  const int st = dev_alloc(bytes > 0 ? bytes : 16, p->stream, out);
-  if (!st) p->bufs.push_back(*out);
+  DevBlock b;
+  const int st = b.alloc(bytes > 0 ? bytes : 16, p->stream);
+  *out = b.p;
+  if (!st) p->bufs.push_back(std::move(b));      // (bufs holds live blocks only)
   return st;
 }
 
-// start[m] of the listed nodes -> host (one gather kernel, one copy, one sync).
-// Pinned landing buffer of the level totals, per thread, grown on demand (a copy into pageable
-// memory takes the runtime's staged path).
+}  // namespace
+
+// Pinned landing buffer of the level totals (and of tree.hip's count pass), per thread, grown on
+// demand (a copy into pageable memory takes the runtime's staged path).
 int64_t* pinned_totals(size_t n) {
   thread_local int64_t* buf = nullptr;
   thread_local size_t cap = 0;
@@ -704,6 +707,9 @@ int64_t* pinned_totals(size_t n) {
   return buf;
 }
 
+namespace {
+
+// start[m] of the listed nodes -> host (one gather kernel, one copy, one sync).
 // *batch_bytes (when given): the batch's row bytes, offs[nrows], copied with the totals into the
 // same pinned buffer (one word past them).
 int level_totals(const LvPlan& p, const std::vector<int32_t>& list, const uint8_t* rows,
@@ -736,11 +742,7 @@ int level_totals(const LvPlan& p, const std::vector<int32_t>& list, const uint8_
 
 }  // namespace
 
-void lv_free(LvPlan* p) {
-  if (!p) return;
-  for (void* b : p->bufs) dev_free(b, p->stream);
-  delete p;
-}
+void lv_free(LvPlan* p) { delete p; }
 
 int lv_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, int64_t nrows,
                hipStream_t hs, LvPlan** out, std::vector<int64_t>* totals) {
@@ -749,7 +751,8 @@ int lv_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, i
   int device = 0;
   (void)hipGetDevice(&device);
   keep_pool(device);                                // per-level syncs must not unmap the pool
-  LvPlan* p = new LvPlan();
+  std::unique_ptr<LvPlan> owner(new LvPlan());
+  LvPlan* p = owner.get();
   p->stream = hs;
   p->ntop = s->num_fields;
   p->root = s->root;
@@ -779,10 +782,7 @@ int lv_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, i
   totals->assign(2 * nn, 0);
   int st = FURY_OK;
   int64_t* dev_tot = nullptr;
-  if ((st = pool_alloc(p, 8 * (nn + 1), reinterpret_cast<void**>(&dev_tot)))) {
-    lv_free(p);
-    return st;
-  }
+  if ((st = pool_alloc(p, 8 * (nn + 1), reinterpret_cast<void**>(&dev_tot)))) return st;
   // The counted nodes of level L (m > 0) share one buffer of segments [m_j counts][0], zeroed:
   // lv_count (level 0) or the parent level's lv_expand fills the counts, one segmented scan
   // turns them into starts.
@@ -894,27 +894,25 @@ int lv_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, i
   }
   std::vector<int64_t> bytes;
   if (!st) st = level_totals(*p, strings, rows, offs, hs, dev_tot, &bytes, &batch_bytes);
-  if (st) {
-    lv_free(p);
-    return st;
-  }
+  if (st) return st;
   for (int i = 0; i < nn; i++) (*totals)[2 * i] = p->nodes[i].m;
   for (size_t j = 0; j < strings.size(); j++) (*totals)[2 * strings[j] + 1] = bytes[j];
   // payload bytes past the batch's row bytes: strings that alias other bytes (as above)
   for (int i = 0; i < nn; i++)
-    if ((*totals)[2 * i + 1] > std::max<int64_t>(batch_bytes, 0)) {
-      lv_free(p);
+    if ((*totals)[2 * i + 1] > std::max<int64_t>(batch_bytes, 0))
       return budget_error("nested decode (level engine): more payload bytes of a node than the "
                           "batch has row bytes");
-    }
-  *out = p;
+  *out = owner.release();
   return FURY_OK;
 }
 
 int lv_execute(const LvPlan* p, const GenNode* outs, const uint8_t* rows, const int64_t* offs,
                hipStream_t hs) {
-  LvPlan q = *p;                                   // outputs of this call into a copy
-  q.bufs.clear();
+  LvPlan q;                                        // outputs of this call into a copy of the nodes
+  q.nodes = p->nodes;
+  q.nrows = p->nrows;
+  q.ntop = p->ntop;
+  q.root = p->root;
   std::vector<int32_t> list;
   for (size_t i = 0; i < q.nodes.size(); i++) {
     LvNode& n = q.nodes[i];

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -127,12 +128,11 @@ struct TreePlan {
   int64_t nrows = 0, ntiles = 0;
   int32_t tile_rows = 0, ntop = 0, root = 0;
   uint32_t stage_cap = 0, stage_cap_w = 0;     // LDS stage bytes: count / write pass
-  int64_t* cnt = nullptr;          // scanned [nn][stride] bases (device, plan-owned)
-  int64_t* byt = nullptr;
+  DevBlock cnt, byt;               // scanned [nn][stride] bases
   hipStream_t stream = nullptr;
   // row walk (walk.hip)
   int64_t stride = 0;              // ntiles + 1: [ntiles] holds the total
-  uint32_t* rowpre = nullptr;      // [K][nrows]
+  DevBlock rowpre;                 // [K][nrows] uint32
   int32_t K = 0, nt = 0, ntw = 0;   // count / write tile rows
   uint32_t pool_cap = 0, out_cap = 0;  // write pass: bitmap-window / output-window LDS bytes
   int32_t knode[kWalkMaxK] = {};
@@ -146,13 +146,7 @@ struct TreePlan {
   uint32_t arena_cap = 0;
 };
 
-void tree_free(TreePlan* p) {
-  if (!p) return;
-  dev_free(p->cnt, p->stream);
-  dev_free(p->byt, p->stream);
-  dev_free(p->rowpre, p->stream);
-  delete p;
-}
+void tree_free(TreePlan* p) { delete p; }
 
 namespace {
 
@@ -164,8 +158,8 @@ int tree_launch(const TreePlan& p, bool write, const TNode* dev_nodes, const uin
   a.offs = offs;
   a.nrows = p.nrows;
   a.ntiles = p.ntiles;
-  a.cnt = p.cnt;
-  a.byt = p.byt;
+  a.cnt = p.cnt.as<int64_t>();
+  a.byt = p.byt.as<int64_t>();
   if (const int e = device_error_word(hs, &a.err)) return e;
   a.overflow = overflow;
   a.nn = static_cast<int32_t>(p.nodes.size());
@@ -177,7 +171,7 @@ int tree_launch(const TreePlan& p, bool write, const TNode* dev_nodes, const uin
   a.stride = p.stride;
   a.prefetch = (p.prefetch >> (write ? 0 : 1)) & 1;
   a.skip = write ? knob::walk_skip.load() : 0;
-  a.rowpre = p.rowpre;
+  a.rowpre = p.rowpre.as<uint32_t>();
   a.K = p.K;
   a.pool_cap = p.pool_cap;
   a.out_cap = write ? p.out_cap : 0;
@@ -202,24 +196,59 @@ int tree_launch(const TreePlan& p, bool write, const TNode* dev_nodes, const uin
   return walk_launch(a, write ? p.ntw : p.nt, write, hs);
 }
 
-}  // namespace
-
-// Tile BFS prepare: pass 1 + tile scan + the host sync for the totals.  p->bfs stays false (FURY_OK)
-// when a tile's records outgrow the arena (the caller falls back to the row walk / level engine).
-// The stage is sized from the batch's average row (one more 8-byte read: the batch's bytes).
-int bfs_prepare(TreePlan* p, const uint8_t* rows, const int64_t* offs, int64_t nrows,
-                hipStream_t hs, int64_t* pin, std::vector<int64_t>* totals) {
+// The count pass of the tile BFS and of the row walk, on the plan's geometry: pass 1 into cnt / byt
+// (rowpre: the walk's per-row prefixes), the tile scan, one host sync for the node totals and the
+// overflow word (*overflowed: records outgrew the arena / the walk's windows; `totals` left alone).
+int count_pass(TreePlan* p, const TNode* dev_nodes, const uint8_t* rows, const int64_t* offs,
+               bool want_rowpre, int64_t* pin, std::vector<int64_t>* totals, bool* overflowed) {
   const int nn = static_cast<int>(p->nodes.size());
-  int st = check_hip(hipMemcpyAsync(pin + 2 * kTreeMaxNodes + 1, offs + nrows, 8,
-                                    hipMemcpyDeviceToHost, hs), "hipMemcpyAsync batch bytes");
-  if (!st) st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize");
+  hipStream_t hs = p->stream;
+  *overflowed = false;
+  DevBlock tot;                                // [2 nn totals][overflow word]
+  int st = p->cnt.alloc(8 * nn * p->stride, hs);
+  if (!st) st = p->byt.alloc(8 * nn * p->stride, hs);
+  if (!st && want_rowpre && p->K > 0) st = p->rowpre.alloc(4 * static_cast<size_t>(p->K) * p->nrows, hs);
+  if (!st) st = tot.alloc(8 * (2 * nn + 2), hs);
   if (st) return st;
-  const int64_t bytes = std::max<int64_t>(pin[2 * kTreeMaxNodes + 1], 0);
+  int32_t* overflow = reinterpret_cast<int32_t*>(tot.as<int64_t>() + 2 * nn);
+  if ((st = check_hip(hipMemsetAsync(overflow, 0, 8, hs), "hipMemsetAsync"))) return st;
+  if ((st = tree_launch(*p, false, dev_nodes, rows, offs, overflow, hs))) return st;
+  hipLaunchKernelGGL(tree_tile_scan, dim3(static_cast<unsigned>(2 * nn)), dim3(kScanT), 0, hs,
+                     p->cnt.as<int64_t>(), p->byt.as<int64_t>(), p->ntiles, p->stride, nn,
+                     tot.as<int64_t>());
+  if ((st = check_hip(hipGetLastError(), "tree scan launch"))) return st;
+  if ((st = check_hip(hipMemcpyAsync(pin, tot.p, 8 * (2 * nn + 1), hipMemcpyDeviceToHost, hs),
+                      "hipMemcpyAsync totals")))
+    return st;
+  if ((st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize"))) return st;
+  *overflowed = reinterpret_cast<const int32_t*>(pin + 2 * nn)[0] != 0;
+  if (*overflowed) return FURY_OK;
+  totals->assign(2 * nn, 0);
+  for (int i = 0; i < nn; i++) {
+    (*totals)[2 * i] = pin[i];
+    (*totals)[2 * i + 1] = pin[nn + i];
+  }
+  return FURY_OK;
+}
+
+// Tile BFS prepare: the count pass on up to three tile geometries; p->bfs stays false (FURY_OK)
+// when records outgrow the arena.  The stage: from the batch's average row (batch_bytes < 0: read).
+int bfs_prepare(TreePlan* p, const uint8_t* rows, const int64_t* offs, int64_t batch_bytes,
+                int64_t* pin, std::vector<int64_t>* totals) {
+  const int nn = static_cast<int>(p->nodes.size());
+  if (batch_bytes < 0) {
+    int st = check_hip(hipMemcpyAsync(pin, offs + p->nrows, 8, hipMemcpyDeviceToHost, p->stream),
+                       "hipMemcpyAsync batch bytes");
+    if (!st) st = check_hip(hipStreamSynchronize(p->stream), "hipStreamSynchronize");
+    if (st) return st;
+    batch_bytes = pin[0];
+  }
   const int nt = knob::bfs_threads.load();
-  const double avg = static_cast<double>(bytes) / static_cast<double>(nrows);
-  DeviceTable dt;
-  st = upload_table(p->nodes.data(), p->nodes.size() * sizeof(TNode), hs, &dt);
-  if (st) return st;
+  DeviceTable dt;                             // the node table, uploaded once for every attempt
+  if (const int st = upload_table(p->nodes.data(), p->nodes.size() * sizeof(TNode), p->stream, &dt))
+    return st;
+  const TNode* dev_nodes = static_cast<const TNode*>(dt.dev);
+  const double avg = static_cast<double>(std::max<int64_t>(batch_bytes, 0)) / static_cast<double>(p->nrows);
   // A tile whose records outgrow the arena is retried with half the rows and a larger arena share
   // (container-heavy rows need ~16 B of records per container entry); after three tries the batch
   // goes to the row walk / level engine.
@@ -239,70 +268,26 @@ int bfs_prepare(TreePlan* p, const uint8_t* rows, const int64_t* offs, int64_t n
     p->bnt = nt;
     p->stage_cap = stage;
     p->arena_cap = arena;
-    p->ntiles = (nrows + trows - 1) / trows;
+    p->ntiles = (p->nrows + trows - 1) / trows;
     p->stride = p->ntiles + 1;
-    int64_t* tot = nullptr;
-    int32_t* overflow = nullptr;
-    if (!st) st = dev_alloc(8 * nn * p->stride, hs, reinterpret_cast<void**>(&p->cnt));
-    if (!st) st = dev_alloc(8 * nn * p->stride, hs, reinterpret_cast<void**>(&p->byt));
-    if (!st) st = dev_alloc(8 * (2 * nn + 2), hs, reinterpret_cast<void**>(&tot));
-    if (!st) {
-      overflow = reinterpret_cast<int32_t*>(tot + 2 * nn);
-      st = check_hip(hipMemsetAsync(overflow, 0, 8, hs), "hipMemsetAsync");
-    }
     p->bfs = true;                          // (tree_launch dispatches on it)
-    if (!st) st = tree_launch(*p, false, static_cast<const TNode*>(dt.dev), rows, offs, overflow, hs);
-    if (!st) {
-      hipLaunchKernelGGL(tree_tile_scan, dim3(static_cast<unsigned>(2 * nn)), dim3(kScanT), 0, hs,
-                         p->cnt, p->byt, p->ntiles, p->stride, nn, tot);
-      st = check_hip(hipGetLastError(), "tree scan launch");
-    }
-    if (!st) st = check_hip(hipMemcpyAsync(pin, tot, 8 * (2 * nn + 1), hipMemcpyDeviceToHost, hs),
-                            "hipMemcpyAsync totals");
-    if (!st) st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize");
-    const bool over = !st && reinterpret_cast<const int32_t*>(pin + 2 * nn)[0] != 0;
-    if (!st && !over) {
-      totals->assign(2 * nn, 0);
-      for (int i = 0; i < nn; i++) {
-        (*totals)[2 * i] = pin[i];
-        (*totals)[2 * i + 1] = pin[nn + i];
-      }
-    }
-    dev_free(tot, hs);
+    bool over = false;
+    const int st = count_pass(p, dev_nodes, rows, offs, false, pin, totals, &over);
     if (!st && !over) return FURY_OK;
     p->bfs = false;
-    dev_free(p->cnt, hs);
-    dev_free(p->byt, hs);
-    p->cnt = p->byt = nullptr;
     if (st) return st;
   }
   return FURY_OK;                           // p->bfs false: the caller falls back
 }
 
-// Pass 1 + tile scan + the one host sync.  *out stays NULL (FURY_OK) when the batch needs the
-// level engine: schema beyond the tree tables, or a row whose arrays do not fit the arena.
-int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, int64_t nrows,
-                 hipStream_t hs, TreePlan** out, std::vector<int64_t>* totals) {
-  *out = nullptr;
+// LIST / MAP elements and STRING / BINARY payload bytes are what the passes count.
+bool counted(int32_t t) {
+  return t == FURY_TYPE_LIST || t == FURY_TYPE_MAP || t == FURY_TYPE_STRING || t == FURY_TYPE_BINARY;
+}
+
+// The node table from the schema: types, parents, ordinals, widths, and each level's first node.
+void build_nodes(const fury_schema* s, TreePlan* p) {
   const int nn = static_cast<int>(s->nodes.size());
-  if (knob::nested_decode == 1 || nn > kTreeMaxNodes || nrows <= 0)
-    return FURY_OK;
-  // counted slots (row walk): LIST / MAP elements, STRING / BINARY payload bytes
-  int K = 0;
-  for (int i = 0; i < nn; i++) {
-    const int t = s->nodes[i].type_id;
-    if (t == FURY_TYPE_LIST || t == FURY_TYPE_MAP || t == FURY_TYPE_STRING || t == FURY_TYPE_BINARY) K++;
-  }
-  const bool walk_ok = K <= kWalkMaxK && s->depth <= kWalkMaxDepth;
-  const bool bfs_ok =
-      !s->root && (knob::nested_decode == 4 || (knob::nested_decode == 3 && !walk_ok));
-  if (!walk_ok && !bfs_ok) return FURY_OK;                          // the level engine
-  TreePlan* p = new TreePlan();
-  p->K = K;
-  p->stream = hs;
-  p->nrows = nrows;
-  p->ntop = s->num_fields;
-  p->root = s->root;
   p->nodes.assign(nn, TNode{});
   std::vector<int32_t> level(nn, 0);
   for (int i = 0; i < nn; i++) {
@@ -324,100 +309,73 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
       level[g.first_child + j] = level[i] + 1;
     }
   }
-  {
-    // counted slots numbered subtree by subtree (top-level field order), so that a field group's
-    // slots are contiguous
-    const int ntop = s->root ? 1 : s->num_fields;
-    std::vector<int32_t> kf(std::max(ntop, 1), 0);
-    for (int i = 0; i < nn; i++) {               // breadth-first: a parent before its children
-      TNode& n = p->nodes[i];
-      n.top = i < ntop ? i : p->nodes[n.parent].top;
-      const bool counted = n.type == FURY_TYPE_LIST || n.type == FURY_TYPE_MAP ||
-                           n.type == FURY_TYPE_STRING || n.type == FURY_TYPE_BINARY;
-      if (counted) kf[n.top]++;
-    }
-    std::vector<int32_t> kn(kf.size() + 1, 0);  // first slot of each subtree
-    for (size_t f = 0; f < kf.size(); f++) kn[f + 1] = kn[f] + kf[f];
-    // field groups: consecutive top-level fields, about walk_group_k slots each, at most kMaxGroups
-    const int gk0 = knob::walk_group_k.load();
-    p->ngrp = 1;
-    p->gf[0] = p->gk[0] = 0;
-    if (gk0 > 0 && K > knob::walk_group_min.load() && ntop > 1 && !s->root) {
-      for (int target = gk0;; target *= 2) {
-        int g = 0, acc = 0;
-        for (int f = 0; f < ntop && g < kMaxGroups; f++) {
-          if (acc > 0 && acc + kf[f] > target) {
-            g++;
-            if (g >= kMaxGroups) break;
-            p->gf[g] = f;
-            p->gk[g] = kn[f];
-            acc = 0;
-          }
-          acc += kf[f];
-        }
-        if (g < kMaxGroups) {
-          p->ngrp = g + 1;
-          break;
-        }
-      }
-    }
-    p->gf[p->ngrp] = ntop;
-    p->gk[p->ngrp] = K;
-    p->Kl = 0;
-    for (int g = 0; g < p->ngrp; g++) p->Kl = std::max(p->Kl, p->gk[g + 1] - p->gk[g]);
-    for (int i = 0; i < nn; i++) {               // breadth-first: a parent before its children
-      TNode& n = p->nodes[i];
-      const bool counted = n.type == FURY_TYPE_LIST || n.type == FURY_TYPE_MAP ||
-                           n.type == FURY_TYPE_STRING || n.type == FURY_TYPE_BINARY;
-      n.k = counted ? kn[n.top]++ : -1;
-      if (counted && n.k < kWalkMaxK) p->knode[n.k] = i;
-      if (i < s->num_fields) n.ek = -1;
-      for (int j = 0; j < n.num_children; j++)
-        p->nodes[n.first_child + j].ek = n.type == FURY_TYPE_STRUCT ? n.ek : n.k;
-    }
-    for (int i = nn - 1; i >= 0; i--) {          // children first
-      TNode& n = p->nodes[i];
-      n.walk = n.k >= 0;
-      for (int j = 0; j < n.num_children; j++) n.walk |= p->nodes[n.first_child + j].walk;
-    }
-  }
   for (int i = 0; i < nn; i++) p->nlevels = std::max(p->nlevels, level[i] + 1);
   // breadth-first numbering: each level's nodes are contiguous
   for (int L = 0, i = 0; L <= p->nlevels && L <= kMaxLevels; L++) {
     while (i < nn && level[i] < L) i++;
     p->lvl[L] = i;
   }
-  // pinned landing zone of the totals: one per host thread, kept (a hipHostMalloc / hipHostFree
-  // pair per call cost more host time than the small kernels)
-  static thread_local int64_t* pin = nullptr;
-  static thread_local size_t pin_words = 0;
-  if (pin_words < static_cast<size_t>(2 * nn + 2)) {
-    if (pin) (void)hipHostFree(pin);
-    pin = nullptr;
-    pin_words = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&pin), 8 * (2 * kTreeMaxNodes + 2), hipHostMallocDefault) != hipSuccess) {
-      pin = nullptr;
-      delete p;
-      return set_error(FURY_ERR_DEVICE, "hipHostMalloc (tree plan)");
-    }
-    pin_words = 2 * kTreeMaxNodes + 2;
+}
+
+// The counted slots (p->K of them) numbered subtree by subtree (top-level field order), so that a
+// field group's slots are contiguous, and the field groups.
+void number_slots(const fury_schema* s, TreePlan* p) {
+  const int nn = static_cast<int>(p->nodes.size());
+  const int ntop = s->root ? 1 : s->num_fields;
+  std::vector<int32_t> kf(std::max(ntop, 1), 0);
+  for (int i = 0; i < nn; i++) {               // breadth-first: a parent before its children
+    TNode& n = p->nodes[i];
+    n.top = i < ntop ? i : p->nodes[n.parent].top;
+    if (counted(n.type)) kf[n.top]++;
   }
-  int st = FURY_OK;
-  if (bfs_ok) {
-    st = bfs_prepare(p, rows, offs, nrows, hs, pin, totals);
-    if (st || p->bfs) {                   // a plan, or an error
-      if (st) tree_free(p);
-      else *out = p;
-      return st;
-    }
-    g_bfs_fallbacks.fetch_add(1);        // a tile overflowed the arena: the row walk / level engine
-    if (!walk_ok) {
-      tree_free(p);
-      return FURY_OK;
+  std::vector<int32_t> kn(kf.size() + 1, 0);  // first slot of each subtree
+  for (size_t f = 0; f < kf.size(); f++) kn[f + 1] = kn[f] + kf[f];
+  // field groups: consecutive top-level fields, about walk_group_k slots each, at most kMaxGroups
+  const int gk0 = knob::walk_group_k.load();
+  p->ngrp = 1;
+  p->gf[0] = p->gk[0] = 0;
+  if (gk0 > 0 && p->K > knob::walk_group_min.load() && ntop > 1 && !s->root) {
+    for (int target = gk0;; target *= 2) {
+      int g = 0, acc = 0;
+      for (int f = 0; f < ntop && g < kMaxGroups; f++) {
+        if (acc > 0 && acc + kf[f] > target) {
+          g++;
+          if (g >= kMaxGroups) break;
+          p->gf[g] = f;
+          p->gk[g] = kn[f];
+          acc = 0;
+        }
+        acc += kf[f];
+      }
+      if (g < kMaxGroups) {
+        p->ngrp = g + 1;
+        break;
+      }
     }
   }
-  // a thread per row; the stage holds the tile's rows up to walk_stage bytes (the rest are read
-  // from HBM), the bitmap-window pool walk_pool bytes
+  p->gf[p->ngrp] = ntop;
+  p->gk[p->ngrp] = p->K;
+  p->Kl = 0;
+  for (int g = 0; g < p->ngrp; g++) p->Kl = std::max(p->Kl, p->gk[g + 1] - p->gk[g]);
+  for (int i = 0; i < nn; i++) {               // breadth-first: a parent before its children
+    TNode& n = p->nodes[i];
+    n.k = counted(n.type) ? kn[n.top]++ : -1;
+    if (n.k >= 0 && n.k < kWalkMaxK) p->knode[n.k] = i;
+    if (i < s->num_fields) n.ek = -1;
+    for (int j = 0; j < n.num_children; j++)
+      p->nodes[n.first_child + j].ek = n.type == FURY_TYPE_STRUCT ? n.ek : n.k;
+  }
+  for (int i = nn - 1; i >= 0; i--) {          // children first
+    TNode& n = p->nodes[i];
+    n.walk = n.k >= 0;
+    for (int j = 0; j < n.num_children; j++) n.walk |= p->nodes[n.first_child + j].walk;
+  }
+}
+
+// The row walk's geometry: a thread per row, the stage holds the tile's rows up to walk_stage bytes
+// (the rest from HBM).  False: the write pass fits no workgroup (defensive; the level engine then).
+bool walk_geometry(TreePlan* p) {
+  const int nn = static_cast<int>(p->nodes.size());
   p->nt = knob::walk_threads.load();
   // Field groups read only their fields' slots and payloads: the L2 pull of whole rows (per group)
   // and the count stage cost more than they save (1M beans of 128 counted nodes, groups of 4:
@@ -441,57 +399,64 @@ int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs,
   // The write pass's LDS (cursors: K x rows, node tables, windows) must fit one workgroup: wide
   // schemas (many counted nodes / nodes) step down the tile rows, then the windows.
   const bool pfw = (p->prefetch & 1) != 0;
-  for (;;) {
-    if (walk_write_lds(nn, p->Kl, p->ntw, p->stage_cap_w, p->pool_cap, pfw, p->out_cap) <= kWalkLdsMax) break;
+  auto lds = [&] { return walk_write_lds(nn, p->Kl, p->ntw, p->stage_cap_w, p->pool_cap, pfw, p->out_cap); };
+  while (lds() > kWalkLdsMax) {
     if (p->ntw > p->nt) p->ntw /= 2;
     else if (p->out_cap > 0) p->out_cap = p->out_cap > 4096 ? p->out_cap / 2 : 0;
     else if (p->pool_cap > 0) p->pool_cap = p->pool_cap > 1024 ? p->pool_cap / 2 : 0;
     else if (p->stage_cap_w > 0) p->stage_cap_w = 0;
-    else break;                                 // cannot happen for K <= kWalkMaxK, nn <= 512
+    else return false;
   }
-  if (walk_write_lds(nn, p->Kl, p->ntw, p->stage_cap_w, p->pool_cap, pfw, p->out_cap) > kWalkLdsMax) {
-    tree_free(p);                               // (defensive) the level engine
-    return FURY_OK;
-  }
-  p->ntiles = (nrows + p->tile_rows - 1) / p->tile_rows;
+  p->ntiles = (p->nrows + p->tile_rows - 1) / p->tile_rows;
   p->stride = p->ntiles + 1;
-  int32_t* overflow = nullptr;
-  int64_t* tot = nullptr;
-  DeviceTable dt;
-  if (!st) st = dev_alloc(8 * nn * p->stride, hs, reinterpret_cast<void**>(&p->cnt));
-  if (!st) st = dev_alloc(8 * nn * p->stride, hs, reinterpret_cast<void**>(&p->byt));
-  if (!st && K > 0)
-    st = dev_alloc(4 * static_cast<size_t>(K) * nrows, hs, reinterpret_cast<void**>(&p->rowpre));
-  if (!st) st = dev_alloc(8 * (2 * nn + 2), hs, reinterpret_cast<void**>(&tot));
-  if (!st) {
-    overflow = reinterpret_cast<int32_t*>(tot + 2 * nn);
-    st = check_hip(hipMemsetAsync(overflow, 0, 8, hs), "hipMemsetAsync");
-  }
-  if (!st) st = upload_table(p->nodes.data(), p->nodes.size() * sizeof(TNode), hs, &dt);
-  if (!st) st = tree_launch(*p, false, static_cast<const TNode*>(dt.dev), rows, offs, overflow, hs);
-  if (!st) {
-    hipLaunchKernelGGL(tree_tile_scan, dim3(static_cast<unsigned>(2 * nn)), dim3(kScanT), 0, hs,
-                       p->cnt, p->byt, p->ntiles, p->stride, nn, tot);
-    st = check_hip(hipGetLastError(), "tree scan launch");
-  }
-  if (!st) st = check_hip(hipMemcpyAsync(pin, tot, 8 * (2 * nn + 1), hipMemcpyDeviceToHost, hs),
-                          "hipMemcpyAsync totals");
-  if (!st) st = check_hip(hipStreamSynchronize(hs), "hipStreamSynchronize");
-  const bool over = !st && reinterpret_cast<const int32_t*>(pin + 2 * nn)[0] != 0;
-  if (!st && !over) {
-    totals->assign(2 * nn, 0);
-    for (int i = 0; i < nn; i++) {
-      (*totals)[2 * i] = pin[i];
-      (*totals)[2 * i + 1] = pin[nn + i];
+  return true;
+}
+
+}  // namespace
+
+// Pass 1 + tile scan + the one host sync.  *out stays NULL (FURY_OK) when the batch needs the
+// level engine: schema beyond the tree tables, or a row whose arrays do not fit the arena.
+// batch_bytes: offs[nrows] where the caller has read it, -1 otherwise (the tile BFS reads it).
+int tree_prepare(const fury_schema* s, const uint8_t* rows, const int64_t* offs, int64_t nrows,
+                 int64_t batch_bytes, hipStream_t hs, TreePlan** out, std::vector<int64_t>* totals) {
+  *out = nullptr;
+  const int nn = static_cast<int>(s->nodes.size());
+  if (knob::nested_decode == 1 || nn > kTreeMaxNodes || nrows <= 0)
+    return FURY_OK;
+  int K = 0;
+  for (int i = 0; i < nn; i++) K += counted(s->nodes[i].type_id);
+  const bool walk_ok = K <= kWalkMaxK && s->depth <= kWalkMaxDepth;
+  const bool bfs_ok =
+      !s->root && (knob::nested_decode == 4 || (knob::nested_decode == 3 && !walk_ok));
+  if (!walk_ok && !bfs_ok) return FURY_OK;                          // the level engine
+  std::unique_ptr<TreePlan> p(new TreePlan());
+  p->K = K;
+  p->stream = hs;
+  p->nrows = nrows;
+  p->ntop = s->num_fields;
+  p->root = s->root;
+  build_nodes(s, p.get());
+  number_slots(s, p.get());
+  int64_t* pin = pinned_totals(2 * kTreeMaxNodes + 2);
+  if (!pin) return set_error(FURY_ERR_DEVICE, "hipHostMalloc (tree plan)");
+  if (bfs_ok) {
+    const int st = bfs_prepare(p.get(), rows, offs, batch_bytes, pin, totals);
+    if (st) return st;
+    if (p->bfs) {
+      *out = p.release();
+      return FURY_OK;
     }
+    g_bfs_fallbacks.fetch_add(1);        // a tile overflowed the arena: the row walk / level engine
+    if (!walk_ok) return FURY_OK;
   }
-  dev_free(tot, hs);
-  if (st || over) {
-    tree_free(p);
-    return st;
-  }
-  *out = p;
-  return FURY_OK;
+  if (!walk_geometry(p.get())) return FURY_OK;       // (defensive) the level engine
+  DeviceTable dt;
+  int st = upload_table(p->nodes.data(), p->nodes.size() * sizeof(TNode), hs, &dt);
+  if (st) return st;
+  bool over = false;
+  st = count_pass(p.get(), static_cast<const TNode*>(dt.dev), rows, offs, true, pin, totals, &over);
+  if (!st && !over) *out = p.release();
+  return st;
 }
 
 int tree_execute(const TreePlan* p, const GenNode* outs, const uint8_t* rows, const int64_t* offs,

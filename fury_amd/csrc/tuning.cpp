@@ -207,6 +207,7 @@ constexpr struct {
     {"decode_budget_errors", as_i32<budget_errors>},
     {"var_dec_rows_rejected", as_i32<var_dec_rows_rejected>},
     {"bfs_fallbacks", as_i32<bfs_fallbacks>},
+    {"workspace_live", as_i32<dev_live_blocks>},           // cached device blocks handed out now
 };
 
 }  // namespace

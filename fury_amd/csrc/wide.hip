@@ -647,51 +647,59 @@ int launch_encode_wide(const VarArgs& a, const int64_t* offs, uint8_t* rows, int
 // the output capacities, as dec_tile_plan) next to the four per-wave images.
 namespace {
 constexpr uint32_t kWideImg = 2048;
-}  // namespace
-
-namespace {
-// The decode's LDS plan: the stage (~64 rows of the estimated row size) and the per-wave images.
-struct WideGeom {
-  int nseq = 0, th = 256;
-  uint32_t stage = 0, imgs = 0;
-  int64_t nt = 0;
-};
 WideGeom wide_geom(const VarArgs& a, double avg_row = -1);
+double wide_row_estimate(const VarArgs& a);
+uint32_t wide_stage_bytes(double row);
+
+// Launches the instance for g.th threads per tile that `pick` names, one workgroup per tile, with
+// `lds` bytes of dynamic LDS.
+template <class Pick, class... Args>
+void wide_launch(const WideGeom& g, size_t lds, hipStream_t stream, Pick pick, Args... args) {
+  auto go = [&](auto threads) {
+    auto kern = pick(threads);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(g.nt)), dim3(decltype(threads)::value), lds,
+                       stream, args...);
+  };
+  if (g.th == 1024) go(std::integral_constant<int, 1024>());
+  else if (g.th == 512) go(std::integral_constant<int, 512>());
+  else go(std::integral_constant<int, 256>());
+}
+
+// Count pass + scan: ws = [nseq x nt counts -> tile bases][total][scan scratch].
+void wide_count(const WideGeom& g, const VarArgs& a, const uint8_t* rows, const int64_t* offs,
+                int64_t* ws, hipStream_t stream) {
+  wide_launch(g, g.stage, stream,
+              [](auto th) { return wide_count_kernel<decltype(th)::value>; }, a, rows, offs, ws, g.nt,
+              g.stage);
+  const int64_t m = static_cast<int64_t>(g.nseq) * g.nt;
+  device_scan(ws, m, ws + m, ws + m + 1, stream);
+}
+
+void wide_write(const WideGeom& g, const VarArgs& a, const uint8_t* rows, const int64_t* offs,
+                const int64_t* ws, bool offsets_only, hipStream_t stream) {
+  wide_launch(g, static_cast<size_t>(g.stage) + g.imgs, stream,
+              [](auto th) { return wide_write_kernel<decltype(th)::value>; }, a, rows, offs, ws, g.nt,
+              g.stage, kWideImg, offsets_only ? 1 : 0);
+}
+
+int64_t wide_ws_words(const WideGeom& g) {
+  const int64_t m = static_cast<int64_t>(g.nseq) * g.nt;
+  return m + 1 + scan_workspace(std::max<int64_t>(m, 1));
+}
 }  // namespace
 
 int launch_decode_wide(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
                        bool offsets_only) {
   if (a.nrows == 0) return FURY_OK;
   const WideGeom g = wide_geom(a);
-  const int nseq = g.nseq;
-  const uint32_t stage = g.stage, imgs = g.imgs;
-  const int64_t nt = g.nt;
-  const int th = g.th;
-  int64_t* ws = nullptr;                   // [nseq x nt counts][total][scan scratch]
-  const int64_t m = static_cast<int64_t>(nseq) * nt;
-  int st = dev_alloc((m + 1 + scan_workspace(std::max<int64_t>(m, 1))) * 8, stream,
-                     reinterpret_cast<void**>(&ws));
+  DevBlock ws;
+  const int st = ws.alloc(wide_ws_words(g) * 8, stream);
   if (st) return st;
-  const size_t lds = static_cast<size_t>(stage) + imgs;
-  auto go = [&](auto count, auto write, int threads) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(write),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(count),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(stage));
-    if (nseq > 0) {
-      hipLaunchKernelGGL(count, dim3(static_cast<unsigned>(nt)), dim3(threads), stage, stream, a,
-                         rows, offs, ws, nt, stage);
-      device_scan(ws, m, ws + m, ws + m + 1, stream);
-    }
-    hipLaunchKernelGGL(write, dim3(static_cast<unsigned>(nt)), dim3(threads), lds, stream, a, rows,
-                       offs, ws, nt, stage, kWideImg, offsets_only ? 1 : 0);
-  };
-  if (th == 1024) go(wide_count_kernel<1024>, wide_write_kernel<1024>, 1024);
-  else if (th == 512) go(wide_count_kernel<512>, wide_write_kernel<512>, 512);
-  else go(wide_count_kernel<256>, wide_write_kernel<256>, 256);
-  st = check_hip(hipGetLastError(), "wide decode launch");
-  dev_free(ws, stream);
-  return st;
+  if (g.nseq > 0) wide_count(g, a, rows, offs, ws.as<int64_t>(), stream);
+  wide_write(g, a, rows, offs, ws.as<int64_t>(), offsets_only, stream);
+  return check_hip(hipGetLastError(), "wide decode launch");
 }
 
 // Plan form (fury_decode_prepare / fury_decode_execute): the count pass and the
@@ -704,37 +712,24 @@ __global__ void wide_totals_kernel(const int64_t* ws, int64_t nt, int32_t nseq, 
 }
 
 int wide_prepare(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
-                 WidePlan* wp, std::vector<int64_t>* seq_totals) {
-  // the stage is sized from the batch's average row (one 8-byte read)
-  int64_t bytes = 0;
-  if (a.nrows > 0) {
-    int st = check_hip(hipMemcpyAsync(&bytes, offs + a.nrows, 8, hipMemcpyDeviceToHost, stream),
-                       "hipMemcpyAsync batch bytes");
+                 int64_t batch_bytes, WidePlan* wp, std::vector<int64_t>* seq_totals) {
+  // the stage is sized from the batch's average row (one 8-byte read where the caller has not
+  // made it)
+  int st = FURY_OK;
+  if (a.nrows > 0 && batch_bytes < 0) {
+    st = check_hip(hipMemcpyAsync(&batch_bytes, offs + a.nrows, 8, hipMemcpyDeviceToHost, stream),
+                   "hipMemcpyAsync batch bytes");
     if (!st) st = check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");
     if (st) return st;
   }
-  const WideGeom g = wide_geom(a, a.nrows > 0 ? static_cast<double>(bytes) / a.nrows : -1.0);
-  wp->nt = g.nt;
-  wp->nseq = g.nseq;
-  wp->stream = stream;
+  wp->g = wide_geom(a, a.nrows > 0 ? static_cast<double>(batch_bytes) / a.nrows : -1.0);
+  const WideGeom& g = wp->g;
   seq_totals->assign(g.nseq, 0);
   if (a.nrows == 0 || g.nseq == 0) return FURY_OK;
-  const int64_t m = static_cast<int64_t>(g.nseq) * g.nt;
-  int st = dev_alloc((m + 1 + scan_workspace(std::max<int64_t>(m, 1)) + g.nseq + 1) * 8, stream,
-                     reinterpret_cast<void**>(&wp->ws));
-  if (st) return st;
-  int64_t* ws = wp->ws;
-  int64_t* tot = ws + m + 1 + scan_workspace(std::max<int64_t>(m, 1));
-  auto go = [&](auto count, int threads) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(count),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(g.stage));
-    hipLaunchKernelGGL(count, dim3(static_cast<unsigned>(g.nt)), dim3(threads), g.stage, stream, a,
-                       rows, offs, ws, g.nt, g.stage);
-  };
-  if (g.th == 1024) go(wide_count_kernel<1024>, 1024);
-  else if (g.th == 512) go(wide_count_kernel<512>, 512);
-  else go(wide_count_kernel<256>, 256);
-  device_scan(ws, m, ws + m, ws + m + 1, stream);
+  if ((st = wp->ws.alloc((wide_ws_words(g) + g.nseq + 1) * 8, stream))) return st;
+  int64_t* ws = wp->ws.as<int64_t>();
+  int64_t* tot = ws + wide_ws_words(g);
+  wide_count(g, a, rows, offs, ws, stream);
   hipLaunchKernelGGL(wide_totals_kernel, dim3(static_cast<unsigned>((g.nseq + 256) / 256)), dim3(256),
                      0, stream, ws, g.nt, g.nseq, tot);
   if ((st = check_hip(hipGetLastError(), "wide prepare launch"))) return st;
@@ -750,53 +745,50 @@ int wide_prepare(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hip
 int wide_execute(const VarArgs& a, const uint8_t* rows, const int64_t* offs, hipStream_t stream,
                  const WidePlan& wp) {
   if (a.nrows == 0) return FURY_OK;
-  const WideGeom g = wide_geom(a);
-  const size_t lds = static_cast<size_t>(g.stage) + g.imgs;
-  auto go = [&](auto write, int threads) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(write),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    hipLaunchKernelGGL(write, dim3(static_cast<unsigned>(g.nt)), dim3(threads), lds, stream, a, rows,
-                       offs, wp.ws, g.nt, g.stage, kWideImg, 0);
-  };
-  if (g.th == 1024) go(wide_write_kernel<1024>, 1024);
-  else if (g.th == 512) go(wide_write_kernel<512>, 512);
-  else go(wide_write_kernel<256>, 256);
+  // Threads, images and tiles are the prepare's; the stage stays sized from the output capacities
+  // (from the true average row the 33-field write ran 0.5 % slower: DESIGN.md 4e, the plan's numbers).
+  WideGeom g = wp.g;
+  g.stage = wide_stage_bytes(wide_row_estimate(a));
+  wide_write(g, a, rows, offs, wp.ws.as<int64_t>(), false, stream);
   return check_hip(hipGetLastError(), "wide execute launch");
 }
 
-void wide_free(WidePlan* wp) {
-  if (!wp) return;
-  dev_free(wp->ws, wp->stream);
-  delete wp;
-}
+void wide_free(WidePlan* wp) { delete wp; }
 
 namespace {
-// avg_row >= 0: the batch's average row bytes (the prepare, which has no output capacities to
-// estimate it from)
-WideGeom wide_geom(const VarArgs& a, double avg_row) {
-  WideGeom g;
-  int nseq = 0;
+// A row's bytes estimated from the output capacities (as dec_tile_plan).
+double wide_row_estimate(const VarArgs& a) {
   double row = a.fixed_size;
   for (int k = 0; k < a.ncols; k++) {
     const VarCol& c = a.htab ? a.htab[k] : a.col[k];
     const double per = a.nrows > 0 && c.capacity > 0 ? static_cast<double>(c.capacity) / a.nrows : 16.0;
-    if (c.kind == kBytes || c.kind == kListFixed) nseq++;
     if (c.kind == kDecimal) row += 16;
     if (c.kind == kBytes) row += per + 4;
     if (c.kind == kListFixed) row += 12 + per * (c.width == 0 ? 1 : c.width) + 4;
   }
-  const uint32_t bit_cap = ((kWideImg / 8 + 4 * 16) + 15) & ~15u;
-  const int th = knob::wide_threads.load();
-  const uint32_t imgs = static_cast<uint32_t>(th / 64) * (kWideImg + bit_cap);
-  // the stage: the tile's estimated row bytes (+3 %), at least 1 KB, at most 96 KB (rows past it
-  // are read from HBM)
-  if (avg_row >= 0) row = avg_row;
+  return row;
+}
+
+// The stage: the tile's estimated row bytes (+3 %), at least 1 KB, at most 96 KB (rows past it are
+// read from HBM).
+uint32_t wide_stage_bytes(double row) {
   const uint32_t want = static_cast<uint32_t>(std::min<double>(row * kWideRows * 1.03 + 64, 96.0 * 1024));
-  g.stage = (std::max<uint32_t>(want, 1024) + 15) & ~15u;
+  return (std::max<uint32_t>(want, 1024) + 15) & ~15u;
+}
+
+// avg_row >= 0: the batch's average row bytes (the prepare, which has no output capacities to
+// estimate it from)
+WideGeom wide_geom(const VarArgs& a, double avg_row) {
+  WideGeom g;
+  for (int k = 0; k < a.ncols; k++) {
+    const VarCol& c = a.htab ? a.htab[k] : a.col[k];
+    if (c.kind == kBytes || c.kind == kListFixed) g.nseq++;
+  }
+  const uint32_t bit_cap = ((kWideImg / 8 + 4 * 16) + 15) & ~15u;
+  g.th = knob::wide_threads.load();
+  g.imgs = static_cast<uint32_t>(g.th / 64) * (kWideImg + bit_cap);
+  g.stage = wide_stage_bytes(avg_row >= 0 ? avg_row : wide_row_estimate(a));
   g.nt = (a.nrows + kWideRows - 1) / kWideRows;
-  g.nseq = nseq;
-  g.th = th;
-  g.imgs = imgs;
   return g;
 }
 }  // namespace

@@ -68,7 +68,7 @@ KNOBS = {
 # fury_get_tuning only
 COUNTERS = ["lookback_timeouts", "unframe_walks", "unframe_repairs", "host_direct", "err_slots",
             "err_slots_quarantined", "thread_key_exits", "err_slot_last_key", "decode_budget_errors",
-            "var_dec_rows_rejected", "bfs_fallbacks"]
+            "var_dec_rows_rejected", "bfs_fallbacks", "workspace_live"]
 
 
 def _lib():
