@@ -6,7 +6,18 @@ HIP kernels behind the C ABI in include/fury_row.h (libfury_row.so, built in-tre
 """
 from . import types  # noqa: F401
 
-__all__ = ["types", "hash_bytes", "hash_null"]
+_KEYS = ("KeySide", "keys_equal_into", "bind_keys_equal", "keys_equal", "candidate_pairs",
+         "join_pairs")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS]
+
+
+def __getattr__(name):
+    """The key-equality and join functions of ``fury_amd.keys``, imported on first use (they need
+    torch and the library; ``import fury_amd`` alone does not)."""
+    if name in _KEYS:
+        from . import keys
+        return getattr(keys, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def hash_bytes(b, seed: int = 0) -> int:

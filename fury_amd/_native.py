@@ -55,6 +55,13 @@ class FuryConcatSource(ctypes.Structure):
                 ("nrows", ctypes.c_int64)]
 
 
+class FuryKeySide(ctypes.Structure):
+    _fields_ = [("schema", ctypes.c_void_p), ("fields", ctypes.POINTER(ctypes.c_int32)),
+                ("rows", ctypes.c_void_p), ("row_offsets", ctypes.c_void_p),
+                ("nrows", ctypes.c_int64), ("indices", ctypes.c_void_p)]
+
+
+KEYS_NULL_EQUAL = 1
 PARTITION_MAX_PARTS = 65535
 CONCAT_MAX_SOURCES = 32
 
@@ -99,6 +106,8 @@ SIGNATURES = {
                                      _P]),
     "fury_hash_bytes": (_U32, [_P, _I64, _U32]),
     "fury_hash_null": (_U32, [_U32]),
+    "fury_row_keys_equal": (ctypes.c_int, [ctypes.POINTER(FuryKeySide), ctypes.POINTER(FuryKeySide),
+                                           _I32, _I64, _I32, _P, _P, _P]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

@@ -1286,6 +1286,82 @@ int fury_row_hash(const fury_schema* s, const int32_t* fields, int32_t num_keys,
   });
 }
 
+// Key equality of row pairs (keys_equal.hip): BinaryRow's getters on both rows, value against value.
+int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
+                        int64_t num_pairs, int32_t flags, uint8_t* out_equal, uint32_t* out_mask,
+                        void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_keys_equal");
+  int st = check_required(f, "left", left);
+  if (st) return st;
+  if ((st = check_required(f, "right", right))) return st;
+  const fury_key_side* sides[2] = {left, right};
+  const std::string names[2] = {f + ": left", f + ": right"};
+  for (int s = 0; s < 2; s++) {
+    // `fields` stands in for the column table check_selection wants, as in fury_row_hash
+    st = check_selection(sides[s]->schema, sides[s]->fields, num_keys, sides[s]->nrows, sides[s]->fields,
+                         names[s], "has no row fields to compare",
+                         "there is no route: compare a subset of the keys and AND the results");
+    if (st) return st;
+    for (int j = 0; j < num_keys; j++) {
+      const fury_schema* sc = sides[s]->schema;
+      const int32_t k = sides[s]->fields[j];
+      if (sc->plan[k].kind == kOther || sc->plan[k].kind == kListFixed)
+        return set_error(FURY_ERR_UNSUPPORTED,
+                         names[s] + ": field " + std::to_string(k) + " (" + sc->fields[k].name +
+                             ") is a LIST / STRUCT / MAP: its stored bytes are not canonical (null "
+                             "slots keep stale contents), so it cannot be a key");
+    }
+  }
+  for (int j = 0; j < num_keys; j++) {
+    const int32_t kl = left->fields[j], kr = right->fields[j];
+    const FieldPlan &pl = left->schema->plan[kl], &pr = right->schema->plan[kr];
+    if (pl.type_id != pr.type_id)
+      return invalid(f, "key " + std::to_string(j) + ": left field " + std::to_string(kl) + " (" +
+                            left->schema->fields[kl].name + ") has type " + std::to_string(pl.type_id) +
+                            ", right field " + std::to_string(kr) + " (" +
+                            right->schema->fields[kr].name + ") has type " + std::to_string(pr.type_id));
+  }
+  if ((st = check_count(f, "num_pairs", num_pairs))) return st;
+  for (int s = 0; s < 2; s++)
+    if (!sides[s]->indices && sides[s]->nrows < num_pairs)
+      return invalid(names[s], "nrows " + std::to_string(sides[s]->nrows) + " < num_pairs " +
+                                   std::to_string(num_pairs) + " and there are no indices");
+  if (flags & ~FURY_KEYS_NULL_EQUAL) return invalid(f, "unknown flags " + std::to_string(flags));
+  if (!out_equal && !out_mask) return invalid(f, "out_equal and out_mask are both null");
+  if ((st = check_aligned(f, 4, {{"out_mask", out_mask}}))) return st;
+  for (int s = 0; s < 2; s++)
+    if ((st = check_aligned(names[s], 8, {{"indices", sides[s]->indices},
+                                          {"row_offsets", sides[s]->row_offsets}})))
+      return st;
+  if (num_pairs == 0) return FURY_OK;
+  KeysEqualArgs a{};
+  for (int s = 0; s < 2; s++) {
+    const fury_schema* sc = sides[s]->schema;
+    if ((st = check_source(names[s], sides[s]->rows, sides[s]->row_offsets, rows_of(sc), true, &a.side[s])))
+      return st;
+    a.side[s].nrows = sides[s]->nrows;
+    a.side[s].indices = sides[s]->indices;
+    a.side[s].bitmap_bytes = sc->bitmap_bytes;
+    a.side[s].fixed_size = sc->fixed_size;
+  }
+  if ((num_pairs + 255) / 256 > INT32_MAX) return invalid(f, "batch too large");
+  a.nkeys = num_keys;
+  a.num_pairs = num_pairs;
+  a.flags = flags;
+  a.out_equal = out_equal;
+  a.out_mask = out_mask;
+  for (int j = 0; j < num_keys; j++) {
+    const FieldPlan& p = left->schema->plan[left->fields[j]];
+    KeyRec& v = a.key[j];
+    v.left_slot = left->fields[j];
+    v.right_slot = right->fields[j];
+    v.kind = p.kind;
+    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+  }
+  return launch_checked(hs, &a, [&] { return launch_keys_equal(a, hs); });
+}
+
 // H of rule 1 on the host: a CPU worker routes a lookup key to the partition the device chose.
 uint32_t fury_hash_bytes(const void* bytes, int64_t len, uint32_t seed) {
   if (len < 0 || len > INT32_MAX || (len > 0 && !bytes)) {

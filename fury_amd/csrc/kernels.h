@@ -429,6 +429,44 @@ __host__ __device__ inline uint32_t mm3_null(uint32_t h) { return mm3_fmix(h ^ 0
 int launch_hash(const ProjArgs& a, const uint8_t* rows, const int64_t* row_offsets, uint32_t seed,
                 uint32_t num_parts, uint32_t* out_hashes, int32_t* out_part_ids, hipStream_t stream);
 
+// ---- key equality of row pairs: keys_equal.hip ------------------------------------------------------
+// Pair j: the key fields of row side[0].indices[j] (NULL: j) of the left batch against those of row
+// side[1].indices[j] (NULL: j) of the right batch, key[k].left_slot against key[k].right_slot; the
+// rules are numbered in include/fury_row.h.  out_equal[j] = 0 / 1, bit j of out_mask the same (whole
+// 32-bit words, tail bits zero); either may be NULL.  Bounds = "Decode bounds" above per side, against
+// that side's own total: an index outside [0, nrows), a row that fails row_ok or a key value that
+// fails span_ok makes the pair unequal whatever the flags and raises kErrBounds with j.
+// row_offsets NULL: fixed-size rows.  Asynchronous on `stream`, no workspace.
+constexpr int kMaxEqualKeys = kMaxProjCols;
+struct KeySide {
+  const uint8_t* rows;
+  const int64_t* row_offsets;         // NULL for fixed-size rows
+  int64_t nrows;
+  const int64_t* indices;             // num_pairs of them (device) or NULL
+  int32_t bitmap_bytes;
+  int32_t fixed_size;
+};
+// One key position.  Indexed wave-uniformly (scalar loads): every member >= 4 bytes, see FixedCol.
+struct KeyRec {
+  int32_t left_slot;                  // field index in the left schema
+  int32_t right_slot;                 // ... in the right one
+  int32_t kind;                       // FieldKind: kFixed / kBool / kBytes / kDecimal
+  int32_t width;                      // kFixed: 1 / 2 / 4 / 8; kBool: 1; kDecimal: 16
+};
+struct KeysEqualArgs {
+  KeySide side[2];
+  KeyRec key[kMaxEqualKeys];
+  int64_t num_pairs;
+  int32_t nkeys;
+  int32_t flags;                      // FURY_KEYS_NULL_EQUAL
+  uint8_t* out_equal;
+  uint32_t* out_mask;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(KeysEqualArgs) <= 4096, "KeysEqualArgs must fit the kernel argument block");
+// FURY_ERR_INVALID_ARGUMENT ("batch too large") for a pair count the grid cannot index.
+int launch_keys_equal(const KeysEqualArgs& a, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

@@ -478,6 +478,63 @@ int fury_row_hash(const fury_schema* schema, const int32_t* fields, int32_t num_
 uint32_t fury_hash_bytes(const void* bytes, int64_t len, uint32_t seed);
 uint32_t fury_hash_null(uint32_t seed);
 
+/* Key equality -- the verify step of an equi-join, a group-by or a de-duplication: do the key fields
+ * of row i of one batch equal the key fields of row j of another?  The batch form of reading both
+ * rows' key fields with BinaryRow's getters and comparing the values, answered from the row bytes with
+ * nothing decoded.  fury_row_hash finds candidates (a 32-bit hash collides); this call decides them.
+ * The definition is normative, so that a worker in any language agrees with the device:
+ *   1. Pairs.  Pair j compares row L = left.indices[j] (left.indices == NULL: L = j) of the left batch
+ *      with row R = right.indices[j] (or j) of the right batch, key position by key position:
+ *      left.fields[k] is compared with right.fields[k], 0 <= k < num_keys.
+ *   2. Key positions.  Both fields null: equal iff FURY_KEYS_NULL_EQUAL is set in `flags`.  Exactly
+ *      one null: not equal.  Neither null: equal iff their value_bytes have the same length and the
+ *      same bytes, value_bytes being rule 3 of fury_row_hash (the bytes fury_row_project would produce
+ *      for the field).  BOOL is one byte, 0 or 1: any non-zero stored byte is 1.  Floats compare as
+ *      their raw bits: -0.0 != 0.0, and two NaNs are equal iff their payloads are.  Padding bytes after
+ *      a payload are never compared.
+ *   3. Outputs.  out_equal[j] (device uint8, num_pairs entries) = 1 iff every key position is equal,
+ *      else 0.  Bit j of out_mask (device uint32 words, word j / 32, LSB first: the convention of
+ *      fury_row_filter's row_mask) is the same value; all (num_pairs + 31) / 32 words are written
+ *      whole, the bits at or past num_pairs zero.  Either output may be NULL, not both.
+ *   4. Consequence.  With FURY_KEYS_NULL_EQUAL, a pair that is equal has equal fury_row_hash values on
+ *      both sides (each side hashed over its own key fields, in key order) for any seed: unequal
+ *      hashes prove inequality.
+ *   5. Bounds are the "Decode bounds" as fury_row_hash applies them, per side, against that side's own
+ *      [0, row_offsets[nrows]) (is_fixed: [0, nrows * fixed_size)).  A failure is an index outside
+ *      [0, nrows), a row whose header leaves the batch, a key value whose span leaves the batch, or a
+ *      key value whose size is negative.  Any failure makes the pair NOT EQUAL WHATEVER THE FLAGS and
+ *      raises FURY_ERR_OUT_OF_BOUNDS on `stream` (fury_device_status), naming the pair number j as
+ *      fury_row_take names its output row.  All keys of a pair are always examined for null bits and
+ *      bounds, so whether an error is raised does not depend on an earlier key having differed;
+ *      payload bytes are read only where both values are non-null, in bounds and of equal length.
+ *      Nothing outside either batch is read, and slots of fields that are not keys are never looked
+ *      at.
+ *   6. Key types are those of fury_row_hash: a LIST, STRUCT or MAP key returns FURY_ERR_UNSUPPORTED,
+ *      for the reason of hash rule 5.  left.fields[k] and right.fields[k] must have the same type_id,
+ *      else FURY_ERR_INVALID_ARGUMENT naming k and both fields.  The two schemas may differ in every
+ *      other way: other fields, the key fields' slot positions, fixed-size against variable-length
+ *      rows.
+ * 1 <= num_keys <= 64; the checks on each side's `schema` and `fields` and their error codes are
+ * fury_row_hash's.  num_pairs and each nrows are >= 0; a side without `indices` needs nrows >=
+ * num_pairs.  `rows` (device, 8-byte aligned), row_offsets and indices (device, 8-byte aligned) follow
+ * fury_row_take; out_mask is 4-byte aligned.  Unknown bits in `flags` return
+ * FURY_ERR_INVALID_ARGUMENT.  num_pairs == 0 does nothing and returns FURY_OK.  The call is
+ * asynchronous on `stream`, never synchronises with the host and allocates no workspace.
+ * Limits: a value is compared by one lane however long it is; keys of several KB per row run at that
+ * lane's rate. */
+typedef struct fury_key_side {
+  const fury_schema* schema;
+  const int32_t* fields;        /* num_keys key fields, in key order (host) */
+  const void* rows;             /* device, 8-byte aligned */
+  const int64_t* row_offsets;   /* device; ignored for an is_fixed schema, as in fury_row_hash */
+  int64_t nrows;
+  const int64_t* indices;       /* device, num_pairs entries; NULL: pair j uses row j */
+} fury_key_side;
+#define FURY_KEYS_NULL_EQUAL 1  /* two null keys compare equal (group-by); default: they do not (SQL join) */
+int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
+                        int64_t num_pairs, int32_t flags,
+                        uint8_t* out_equal, uint32_t* out_mask, void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
