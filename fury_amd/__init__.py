@@ -8,15 +8,20 @@ from . import types  # noqa: F401
 
 _KEYS = ("KeySide", "keys_equal_into", "bind_keys_equal", "keys_equal", "candidate_pairs",
          "join_pairs")
-__all__ = ["types", "hash_bytes", "hash_null", *_KEYS]
+_GROUP = ("Groups", "group_rows_into", "bind_group", "group_rows", "group_sizes", "distinct")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP]
 
 
 def __getattr__(name):
-    """The key-equality and join functions of ``fury_amd.keys``, imported on first use (they need
-    torch and the library; ``import fury_amd`` alone does not)."""
+    """The key-equality and join functions of ``fury_amd.keys`` and the group functions of
+    ``fury_amd.group``, imported on first use (they need torch and the library; ``import fury_amd``
+    alone does not)."""
     if name in _KEYS:
         from . import keys
         return getattr(keys, name)
+    if name in _GROUP:
+        from . import group
+        return getattr(group, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

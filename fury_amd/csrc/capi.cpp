@@ -1362,6 +1362,65 @@ int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, i
   return launch_checked(hs, &a, [&] { return launch_keys_equal(a, hs); });
 }
 
+// Group ids and distinct rows (group.hip): BinaryRow's getters feeding a LinkedHashMap, null equal to null.
+int fury_row_group(const fury_schema* s, const int32_t* fields, int32_t num_keys, const void* rows,
+                   const int64_t* row_offsets, int64_t nrows, const uint32_t* hashes, int64_t* out_first,
+                   int64_t* out_group_ids, int64_t* out_group_rows, int64_t* out_num_groups, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_group");
+  // `fields` stands in for the column table check_selection wants, as in fury_row_hash
+  int st = check_selection(s, fields, num_keys, nrows, fields, f, "has no row fields to group by",
+                           "there is no route: group by a subset of the keys, then each group by the rest");
+  if (st) return st;
+  for (int j = 0; j < num_keys; j++) {
+    const int32_t k = fields[j];
+    if (s->plan[k].kind == kOther || s->plan[k].kind == kListFixed)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": field " + std::to_string(k) + " (" + s->fields[k].name +
+                           ") is a LIST / STRUCT / MAP: its stored bytes are not canonical (null "
+                           "slots keep stale contents), so it cannot be a key");
+  }
+  if ((st = check_required(f, "out_first", out_first))) return st;
+  if ((st = check_aligned(f, 8, {{"out_first", out_first}, {"out_group_ids", out_group_ids},
+                                 {"out_group_rows", out_group_rows}, {"out_num_groups", out_num_groups}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"hashes", hashes}}))) return st;
+  if (nrows > INT32_MAX) return invalid(f, "batch too large");
+  GroupArgs a{};
+  if (nrows == 0) {                               // no rows, no groups
+    if (!out_num_groups) return FURY_OK;
+    return launch_checked(hs, &a, [&] {
+      return check_hip(hipMemsetAsync(out_num_groups, 0, 8, hs), "fury_row_group: memset");
+    });
+  }
+  if ((st = check_source(f, rows, row_offsets, rows_of(s), true, &a.side))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}}))) return st;
+  a.side.nrows = nrows;
+  a.side.bitmap_bytes = s->bitmap_bytes;
+  a.side.fixed_size = s->fixed_size;
+  a.nkeys = num_keys;
+  a.hashes = hashes;
+  a.out_first = out_first;
+  a.out_group_ids = out_group_ids;
+  a.out_group_rows = out_group_rows;
+  a.out_num_groups = out_num_groups;
+  ProjArgs h{};                                   // the keys as fury_row_hash hashes them
+  h.ncols = num_keys;
+  h.bitmap_bytes = s->bitmap_bytes;
+  h.fixed_size = s->fixed_size;
+  h.nrows = nrows;
+  h.nt = 1;
+  for (int j = 0; j < num_keys; j++) {
+    const FieldPlan& p = s->plan[fields[j]];
+    const int32_t width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+    a.key[j].left_slot = a.key[j].right_slot = fields[j];
+    a.key[j].kind = h.col[j].kind = p.kind;
+    a.key[j].width = h.col[j].width = width;
+    h.col[j].slot = fields[j];
+  }
+  return launch_checked(hs, &a, [&] { return launch_group(a, &h, hs); });
+}
+
 // H of rule 1 on the host: a CPU worker routes a lookup key to the partition the device chose.
 uint32_t fury_hash_bytes(const void* bytes, int64_t len, uint32_t seed) {
   if (len < 0 || len > INT32_MAX || (len > 0 && !bytes)) {

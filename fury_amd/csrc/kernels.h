@@ -467,6 +467,36 @@ static_assert(sizeof(KeysEqualArgs) <= 4096, "KeysEqualArgs must fit the kernel 
 // FURY_ERR_INVALID_ARGUMENT ("batch too large") for a pair count the grid cannot index.
 int launch_keys_equal(const KeysEqualArgs& a, hipStream_t stream);
 
+// ---- group ids and distinct rows by key fields: group.hip ---------------------------------------------
+// Rows of one batch (side; side.indices unused) grouped by the key fields key[k].left_slot (==
+// .right_slot) under fury_row_keys_equal's rule 2 with FURY_KEYS_NULL_EQUAL; the rules are numbered
+// in include/fury_row.h.  out_first[i] = the smallest row of row i's group; out_group_ids[i] = the
+// groups whose first row is below out_first[i]; out_group_rows[g] = the first row of group g, -1 at
+// and past the group count; *out_num_groups = the count.  All but out_first may be NULL.  hashes:
+// nrows entries, equal for rows of equal keys, or NULL: launch_hash of hash_args (the keys as
+// fury_row_hash builds them), seed 0, into workspace.  Bounds = "Decode bounds" above: a row that
+// fails row_ok or a key value that fails span_ok is a group of its own, is never compared and raises
+// kErrBounds with the row.  Asynchronous on `stream`; workspace: group_workspace_bytes.
+struct GroupArgs {
+  KeySide side;
+  KeyRec key[kMaxEqualKeys];
+  int32_t nkeys;
+  int32_t pad_;
+  const uint32_t* hashes;
+  int64_t* out_first;
+  int64_t* out_group_ids;
+  int64_t* out_group_rows;
+  int64_t* out_num_groups;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(GroupArgs) <= 4096, "GroupArgs must fit the kernel argument block");
+int64_t group_table_slots(int64_t nrows);       // the smallest power of two >= 2 nrows
+// 8 bytes per table slot (16 to 32 per row) + 4 per row, + 4 per row without caller hashes, + 8 per
+// row and scan_workspace(nrows) words when any output but out_first is wanted: at most 48 per row.
+int64_t group_workspace_bytes(int64_t nrows, bool own_hashes, bool numbered);
+// FURY_ERR_INVALID_ARGUMENT ("batch too large") for nrows > 2^31 - 1: a slot holds 32 bits of row.
+int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

@@ -1,0 +1,144 @@
+// keys_dev.h -- the comparison of two rows' key fields, shared by the kernels that decide key
+// equality from the row bytes (keys_equal.hip: pairs of two batches; group.hip: a row against the
+// representative of a hash-table slot).  One implementation of rule 2 of fury_row_keys_equal: header
+// words in flight, slot_count, same_bytes and the tail rule.  Design notes: keys_equal.hip.
+#pragma once
+
+#include "project_dev.h"
+
+namespace fury {
+
+namespace {
+
+constexpr int kKeyGroup = 4;                   // keys whose header words are in flight together
+constexpr int kPayWords = 4;                   // payload words per side in flight together
+
+using CKeyRec = __attribute__((address_space(4))) const KeyRec;
+
+__device__ __forceinline__ uint64_t load8(const uint8_t* p) {
+  return *gl(reinterpret_cast<const uint64_t*>(p));
+}
+
+// The 8 batch bytes at s, [s, s + 8) inside [0, total): one aligned load when `al`.
+__device__ __forceinline__ uint64_t pay_word(const uint8_t* rows, int64_t s, int64_t total, bool al) {
+  return al ? load8(rows + s) : batch_word(rows, s, total);
+}
+
+// The `rem` (1..7) bytes at s, [s, s + rem) inside [0, total), in the low bytes of the result: one
+// word when it lies inside the batch, else (the batch's last bytes) by byte -- hash_span's rule.
+__device__ __forceinline__ uint64_t pay_tail(const uint8_t* rows, int64_t s, int rem, int64_t total,
+                                             bool al) {
+  uint64_t v = 0;
+  if (s + 8 <= total) {
+    v = pay_word(rows, s, total, al);
+  } else {
+    for (int i = 0; i < rem; i++) v |= static_cast<uint64_t>(gl(rows)[s + i]) << (8 * i);
+  }
+  return v & (~uint64_t(0) >> (64 - 8 * rem));
+}
+
+// Batch bytes [pl, pl + n) of the left batch == [pr, pr + n) of the right one; both spans lie inside
+// their batches (slot_count).
+__device__ __forceinline__ bool same_bytes(const uint8_t* rl, int64_t pl, int64_t tl, const uint8_t* rr,
+                                           int64_t pr, int64_t tr, int64_t n) {
+  const bool al = ((pl | pr) & 7) == 0;           // every well-formed row: aligned 8-byte loads
+  const int64_t nw = n >> 3;
+  for (int64_t w0 = 0; w0 < nw; w0 += kPayWords) {
+    uint64_t x[kPayWords], y[kPayWords];
+#pragma unroll
+    for (int u = 0; u < kPayWords; u++) {
+      x[u] = y[u] = 0;
+      if (w0 + u < nw) {
+        x[u] = pay_word(rl, pl + 8 * (w0 + u), tl, al);
+        y[u] = pay_word(rr, pr + 8 * (w0 + u), tr, al);
+      }
+    }
+    uint64_t diff = 0;
+#pragma unroll
+    for (int u = 0; u < kPayWords; u++) diff |= x[u] ^ y[u];
+    if (diff) return false;
+  }
+  const int rem = static_cast<int>(n & 7);
+  if (rem == 0) return true;
+  return pay_tail(rl, pl + 8 * nw, rem, tl, al) == pay_tail(rr, pr + 8 * nw, rem, tr, al);
+}
+
+// One side of a pair: the row, whether it can be read, its batch.
+struct PairRow {
+  const uint8_t* rows;
+  int64_t base;                       // absolute row start
+  int64_t total;                      // the batch's row bytes
+  int32_t bitmap_bytes;
+  bool ok;                            // index in [0, nrows) and header inside the batch
+};
+
+// Every key position of the pair pr[0] / pr[1] equal under rule 2 (key[k].left_slot of pr[0] against
+// key[k].right_slot of pr[1]).  Every key is examined for its null bit and bounds whatever the
+// earlier keys gave; `fail` is set (never cleared) when a value's span leaves its batch, and payloads
+// are not read from then on.  A side that is not ok has every key null.  `key` is indexed
+// wave-uniformly (scalar loads).  `fail` is a reference, not a pointer or a returned pair: as a
+// pointer the VAR instantiation of keys_equal took one more VGPR.
+template <bool VAR>
+__device__ __forceinline__ bool pair_keys_equal(const PairRow (&pr)[2], CKeyRec* key, int nkeys,
+                                                bool null_equal, bool& fail) {
+  bool eq = true;
+  for (int k0 = 0; k0 < nkeys; k0 += kKeyGroup) {
+    uint64_t bits[kKeyGroup][2], slot[kKeyGroup][2];
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {         // every header word of the group, both sides
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        bits[u][s] = ~uint64_t(0);                // a row that cannot be read: every key null
+        slot[u][s] = 0;
+        if (k0 + u < nkeys && pr[s].ok) {
+          CKeyRec& c = key[k0 + u];
+          const int32_t f = s == 0 ? c.left_slot : c.right_slot;
+          const uint8_t* hdr = pr[s].rows + pr[s].base;
+          bits[u][s] = load8(hdr + 8 * static_cast<int64_t>(f >> 6));
+          slot[u][s] = load8(hdr + pr[s].bitmap_bytes + 8 * static_cast<int64_t>(f));
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {
+      if (k0 + u >= nkeys) break;
+      CKeyRec& c = key[k0 + u];
+      const int kind = c.kind, width = c.width;
+      bool isnull[2];
+      int64_t n[2];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int32_t f = s == 0 ? c.left_slot : c.right_slot;
+        isnull[s] = (bits[u][s] >> (f & 63)) & 1;
+        n[s] = width;
+        if (VAR && kind >= kBytes && !isnull[s]) {
+          bool bad = false;
+          n[s] = slot_count(kind, width, slot[u][s], pr[s].base, pr[s].rows, pr[s].total, &bad);
+          if (kind == kDecimal) n[s] = 16;
+          if (bad) {
+            fail = true;
+            isnull[s] = true;
+          }
+        }
+      }
+      if (isnull[0] || isnull[1]) {
+        eq = eq && isnull[0] && isnull[1] && null_equal;
+      } else if (VAR && kind >= kBytes) {
+        eq = eq && n[0] == n[1];
+        if (eq && !fail)
+          eq = same_bytes(pr[0].rows, pr[0].base + static_cast<int32_t>(slot[u][0] >> 32), pr[0].total,
+                          pr[1].rows, pr[1].base + static_cast<int32_t>(slot[u][1] >> 32), pr[1].total,
+                          n[0]);
+      } else if (kind == kBool) {
+        eq = eq && ((slot[u][0] & 0xff) != 0) == ((slot[u][1] & 0xff) != 0);
+      } else {                                    // kFixed: the `width` value bytes of the slot
+        eq = eq && ((slot[u][0] ^ slot[u][1]) & (~uint64_t(0) >> (64 - 8 * width))) == 0;
+      }
+    }
+  }
+  return eq;
+}
+
+}  // namespace
+
+}  // namespace fury

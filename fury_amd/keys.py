@@ -5,8 +5,8 @@ The operation is symmetric in two encoders, so it is a set of module-level funct
 batch equal the key fields of row j of another?" from the row bytes (the numbered rules are in
 ``include/fury_row.h``); ``candidate_pairs`` turns two hash arrays into the pairs whose hashes agree,
 in plain torch; ``join_pairs`` composes them with ``RowEncoder.hash_rows`` into the matching row
-pairs of an equi-join.  Group-by and de-duplication are a batch joined with itself under
-``null_equal=True``.
+pairs of an equi-join.  Group-by and de-duplication are ``fury_amd.group_rows`` / ``distinct``
+(fury_row_group), linear in the rows; a batch joined with itself is a join, quadratic in a group.
 """
 from __future__ import annotations
 

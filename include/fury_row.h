@@ -535,6 +535,66 @@ int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, i
                         int64_t num_pairs, int32_t flags,
                         uint8_t* out_equal, uint32_t* out_mask, void* stream);
 
+/* Group ids and distinct rows -- the batch form of reading every row's key fields with BinaryRow's
+ * getters and putting the rows into a LinkedHashMap keyed by the values: which rows of ONE batch have
+ * equal keys, answered from the row bytes with nothing decoded and in time linear in nrows (the
+ * self-join through fury_row_keys_equal is quadratic in the size of a group).  The definition is
+ * normative; the output is a pure function of the batch and the key fields:
+ *   1. Groups.  Two rows are in the same group iff every key position is equal under rule 2 of
+ *      fury_row_keys_equal with FURY_KEYS_NULL_EQUAL: null equals null, null differs from the empty
+ *      string, floats compare as their raw bits (-0.0 != 0.0, NaNs by payload), BOOL is 0 or 1 (any
+ *      non-zero stored byte is 1), padding bytes after a payload are never compared.
+ *   2. First rows.  out_first[i] (device int64, nrows entries, required) = the smallest row number in
+ *      row i's group.  It is deterministic: independent of how the device schedules the rows.
+ *   3. Numbering.  Groups are numbered in the order of their first rows; G = the number of groups.
+ *      out_group_ids[i]  (optional, nrows entries) = the number of groups whose first row is less than
+ *                        out_first[i]: in [0, G).
+ *      out_group_rows[g] (optional, nrows entries) = the first row of group g for g < G, -1 for
+ *                        G <= g < nrows.
+ *      *out_num_groups   (optional, 1 entry) = G.
+ *      Every entry of every given output is written exactly once per call.
+ *      Consequences: (a) fury_row_take at out_group_rows[0 .. G) returns the distinct rows in source
+ *      order (de-duplication keeps the first occurrence); (b) out_group_ids, narrowed to int32, fed to
+ *      fury_row_partition with num_parts = G (G <= FURY_PARTITION_MAX_PARTS) makes every group
+ *      contiguous, groups in order of first occurrence, rows in source order; (c) out_first[i] ==
+ *      out_group_rows[out_group_ids[i]].
+ *   4. Hashes.  hashes == NULL: the call hashes the keys itself, as fury_row_hash does with seed 0,
+ *      into workspace.  hashes != NULL (device uint32, nrows entries): any function of the key values
+ *      will do -- rows with equal keys must have equal entries -- for example the out_hashes of
+ *      fury_row_hash over the same keys with any seed, so a shuffle's hashes are not computed twice.
+ *      The hash only chooses where probing starts and which rows are compared; correctness never
+ *      rests on its quality (all-equal hashes give the same outputs, slowly).  If the caller breaks
+ *      the condition, rows with equal keys may land in different groups; nothing else may happen: no
+ *      read outside the batch, every output is still written, out_first[i] <= i and the numbering of
+ *      rule 3 holds for the groups that were formed.
+ *   5. Bounds are the "Decode bounds" as fury_row_hash applies them.  A row whose header leaves
+ *      [0, row_offsets[nrows]) (is_fixed: [0, nrows * fixed_size)), or a key value whose span leaves
+ *      it or whose size is negative, makes row i a group of its own (out_first[i] = i); the row is
+ *      never entered into the table and never compared with another row, and it raises
+ *      FURY_ERR_OUT_OF_BOUNDS on `stream` (fury_device_status) naming row i.  Nothing outside the
+ *      batch is read, and slots of fields that are not keys are never looked at.
+ *   6. Key types and the checks on `schema`, `fields` and `num_keys`, with their error codes, are those
+ *      of fury_row_hash: 1 <= num_keys <= 64, a LIST, STRUCT or MAP key returns FURY_ERR_UNSUPPORTED.
+ * out_first == NULL returns FURY_ERR_INVALID_ARGUMENT.  `rows`, row_offsets and the int64 outputs are
+ * device memory, 8-byte aligned, `hashes` 4-byte aligned; row_offsets is ignored and may be NULL for an
+ * is_fixed schema, as in fury_row_hash.  nrows == 0 writes *out_num_groups = 0 when it is given and
+ * nothing else.  nrows > 2^31 - 1 returns FURY_ERR_INVALID_ARGUMENT ("batch too large").  The call is
+ * asynchronous on `stream` and never synchronises with the host; argument errors are returned before
+ * any device work.
+ * Workspace (stream-ordered, freed on `stream`): one 8-byte table slot for each of the smallest power
+ * of two >= 2 * nrows slots (16 to 32 bytes per row), 4 bytes per row of slot indices, 4 bytes per row
+ * of hashes when hashes == NULL, and 8 bytes per row (plus nrows / 255 words of scan scratch) when any
+ * output but out_first is given: at most 48 bytes per row.
+ * Limits: a value is compared by one lane however long it is, as in fury_row_keys_equal. */
+int fury_row_group(const fury_schema* schema, const int32_t* fields, int32_t num_keys,
+                   const void* rows, const int64_t* row_offsets, int64_t nrows,
+                   const uint32_t* hashes,      /* device, nrows entries, optional */
+                   int64_t* out_first,          /* device, nrows entries, required */
+                   int64_t* out_group_ids,      /* device, nrows entries, optional */
+                   int64_t* out_group_rows,     /* device, nrows entries, optional */
+                   int64_t* out_num_groups,     /* device, 1 entry, optional */
+                   void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
