@@ -9,12 +9,14 @@ from . import types  # noqa: F401
 _KEYS = ("KeySide", "keys_equal_into", "bind_keys_equal", "keys_equal", "candidate_pairs",
          "join_pairs")
 _GROUP = ("Groups", "group_rows_into", "bind_group", "group_rows", "group_sizes", "distinct")
-__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP]
+_LOOKUP = ("KeyIndex", "index_slots", "build_index_into", "build_index", "lookup_into", "bind_lookup",
+           "lookup", "semi_join", "lookup_join_pairs")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP]
 
 
 def __getattr__(name):
-    """The key-equality and join functions of ``fury_amd.keys`` and the group functions of
-    ``fury_amd.group``, imported on first use (they need torch and the library; ``import fury_amd``
+    """The key-equality and join functions of ``fury_amd.keys``, the group functions of
+    ``fury_amd.group`` and the index functions of ``fury_amd.lookup``, imported on first use (they need torch and the library; ``import fury_amd``
     alone does not)."""
     if name in _KEYS:
         from . import keys
@@ -22,6 +24,10 @@ def __getattr__(name):
     if name in _GROUP:
         from . import group
         return getattr(group, name)
+    if name in _LOOKUP:
+        import importlib                          # `from . import lookup` would ask for "lookup" here again
+        module = importlib.import_module(".lookup", __name__)
+        return module if name == "lookup" else getattr(module, name)      # the module is callable
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

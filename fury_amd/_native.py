@@ -110,6 +110,11 @@ SIGNATURES = {
                                            _I32, _I64, _I32, _P, _P, _P]),
     "fury_row_group": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _P, _P, _P, _P,
                                       _P]),
+    "fury_row_index_slots": (_I64, [_I64]),
+    "fury_row_index_build": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _P, _I64, _P,
+                                            _P]),
+    "fury_row_lookup": (ctypes.c_int, [ctypes.POINTER(FuryKeySide), ctypes.POINTER(FuryKeySide), _I32, _P,
+                                       _I64, _P, _I32, _P, _P, _P]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

@@ -1286,22 +1286,17 @@ int fury_row_hash(const fury_schema* s, const int32_t* fields, int32_t num_keys,
   });
 }
 
-// Key equality of row pairs (keys_equal.hip): BinaryRow's getters on both rows, value against value.
-int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
-                        int64_t num_pairs, int32_t flags, uint8_t* out_equal, uint32_t* out_mask,
-                        void* stream) {
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const std::string f("fury_row_keys_equal");
-  int st = check_required(f, "left", left);
-  if (st) return st;
-  if ((st = check_required(f, "right", right))) return st;
-  const fury_key_side* sides[2] = {left, right};
-  const std::string names[2] = {f + ": left", f + ": right"};
+// Rule 6 of fury_row_keys_equal for the two sides of a key comparison (fury_row_keys_equal: left / right;
+// fury_row_lookup: probe / build): each side's selection, no LIST / STRUCT / MAP key, the same type_id
+// at every key position.
+static int check_key_sides(const std::string& f, const fury_key_side* const (&sides)[2],
+                           const std::string (&names)[2], const char* first, const char* second,
+                           int32_t num_keys) {
   for (int s = 0; s < 2; s++) {
     // `fields` stands in for the column table check_selection wants, as in fury_row_hash
-    st = check_selection(sides[s]->schema, sides[s]->fields, num_keys, sides[s]->nrows, sides[s]->fields,
-                         names[s], "has no row fields to compare",
-                         "there is no route: compare a subset of the keys and AND the results");
+    int st = check_selection(sides[s]->schema, sides[s]->fields, num_keys, sides[s]->nrows, sides[s]->fields,
+                             names[s], "has no row fields to compare",
+                             "there is no route: compare a subset of the keys and AND the results");
     if (st) return st;
     for (int j = 0; j < num_keys; j++) {
       const fury_schema* sc = sides[s]->schema;
@@ -1314,14 +1309,41 @@ int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, i
     }
   }
   for (int j = 0; j < num_keys; j++) {
-    const int32_t kl = left->fields[j], kr = right->fields[j];
-    const FieldPlan &pl = left->schema->plan[kl], &pr = right->schema->plan[kr];
+    const int32_t kl = sides[0]->fields[j], kr = sides[1]->fields[j];
+    const FieldPlan &pl = sides[0]->schema->plan[kl], &pr = sides[1]->schema->plan[kr];
     if (pl.type_id != pr.type_id)
-      return invalid(f, "key " + std::to_string(j) + ": left field " + std::to_string(kl) + " (" +
-                            left->schema->fields[kl].name + ") has type " + std::to_string(pl.type_id) +
-                            ", right field " + std::to_string(kr) + " (" +
-                            right->schema->fields[kr].name + ") has type " + std::to_string(pr.type_id));
+      return invalid(f, "key " + std::to_string(j) + ": " + first + " field " + std::to_string(kl) + " (" +
+                            sides[0]->schema->fields[kl].name + ") has type " + std::to_string(pl.type_id) +
+                            ", " + second + " field " + std::to_string(kr) + " (" +
+                            sides[1]->schema->fields[kr].name + ") has type " + std::to_string(pr.type_id));
   }
+  return FURY_OK;
+}
+
+// The key positions of a two-sided comparison: `left`'s fields against `right`'s.
+static void fill_key_recs(const fury_key_side* left, const fury_key_side* right, int32_t num_keys, KeyRec* key) {
+  for (int j = 0; j < num_keys; j++) {
+    const FieldPlan& p = left->schema->plan[left->fields[j]];
+    KeyRec& v = key[j];
+    v.left_slot = left->fields[j];
+    v.right_slot = right->fields[j];
+    v.kind = p.kind;
+    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+  }
+}
+
+// Key equality of row pairs (keys_equal.hip): BinaryRow's getters on both rows, value against value.
+int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
+                        int64_t num_pairs, int32_t flags, uint8_t* out_equal, uint32_t* out_mask,
+                        void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_keys_equal");
+  int st = check_required(f, "left", left);
+  if (st) return st;
+  if ((st = check_required(f, "right", right))) return st;
+  const fury_key_side* sides[2] = {left, right};
+  const std::string names[2] = {f + ": left", f + ": right"};
+  if ((st = check_key_sides(f, sides, names, "left", "right", num_keys))) return st;
   if ((st = check_count(f, "num_pairs", num_pairs))) return st;
   for (int s = 0; s < 2; s++)
     if (!sides[s]->indices && sides[s]->nrows < num_pairs)
@@ -1351,26 +1373,16 @@ int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, i
   a.flags = flags;
   a.out_equal = out_equal;
   a.out_mask = out_mask;
-  for (int j = 0; j < num_keys; j++) {
-    const FieldPlan& p = left->schema->plan[left->fields[j]];
-    KeyRec& v = a.key[j];
-    v.left_slot = left->fields[j];
-    v.right_slot = right->fields[j];
-    v.kind = p.kind;
-    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
-  }
+  fill_key_recs(left, right, num_keys, a.key);
   return launch_checked(hs, &a, [&] { return launch_keys_equal(a, hs); });
 }
 
-// Group ids and distinct rows (group.hip): BinaryRow's getters feeding a LinkedHashMap, null equal to null.
-int fury_row_group(const fury_schema* s, const int32_t* fields, int32_t num_keys, const void* rows,
-                   const int64_t* row_offsets, int64_t nrows, const uint32_t* hashes, int64_t* out_first,
-                   int64_t* out_group_ids, int64_t* out_group_rows, int64_t* out_num_groups, void* stream) {
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const std::string f("fury_row_group");
-  // `fields` stands in for the column table check_selection wants, as in fury_row_hash
-  int st = check_selection(s, fields, num_keys, nrows, fields, f, "has no row fields to group by",
-                           "there is no route: group by a subset of the keys, then each group by the rest");
+// The key fields of one batch, as fury_row_group and fury_row_index_build check them: the selection, then
+// no LIST / STRUCT / MAP key.  `fields` stands in for the column table check_selection wants, as in
+// fury_row_hash.
+static int check_key_fields(const std::string& f, const fury_schema* s, const int32_t* fields, int32_t num_keys,
+                            int64_t nrows, const char* none, const char* route) {
+  const int st = check_selection(s, fields, num_keys, nrows, fields, f, none, route);
   if (st) return st;
   for (int j = 0; j < num_keys; j++) {
     const int32_t k = fields[j];
@@ -1380,6 +1392,55 @@ int fury_row_group(const fury_schema* s, const int32_t* fields, int32_t num_keys
                            ") is a LIST / STRUCT / MAP: its stored bytes are not canonical (null "
                            "slots keep stale contents), so it cannot be a key");
   }
+  return FURY_OK;
+}
+
+// The keys as fury_row_hash hashes them.
+static void hash_key_args(const fury_schema* s, const int32_t* fields, int32_t num_keys, int64_t nrows,
+                          ProjArgs* h) {
+  h->ncols = num_keys;
+  h->bitmap_bytes = s->bitmap_bytes;
+  h->fixed_size = s->fixed_size;
+  h->nrows = nrows;
+  h->nt = 1;
+  for (int j = 0; j < num_keys; j++) {
+    const FieldPlan& p = s->plan[fields[j]];
+    h->col[j].kind = p.kind;
+    h->col[j].width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+    h->col[j].slot = fields[j];
+  }
+}
+
+// The batch and its keys into the argument block of group.hip's table kernels, after the source checks.
+static int group_batch_args(const std::string& f, const fury_schema* s, const int32_t* fields, int32_t num_keys,
+                            const void* rows, const int64_t* row_offsets, int64_t nrows,
+                            const uint32_t* hashes, GroupArgs* a, ProjArgs* h) {
+  int st = check_source(f, rows, row_offsets, rows_of(s), true, &a->side);
+  if (st) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}}))) return st;
+  a->side.nrows = nrows;
+  a->side.bitmap_bytes = s->bitmap_bytes;
+  a->side.fixed_size = s->fixed_size;
+  a->nkeys = num_keys;
+  a->hashes = hashes;
+  hash_key_args(s, fields, num_keys, nrows, h);
+  for (int j = 0; j < num_keys; j++) {
+    a->key[j].left_slot = a->key[j].right_slot = fields[j];
+    a->key[j].kind = h->col[j].kind;
+    a->key[j].width = h->col[j].width;
+  }
+  return FURY_OK;
+}
+
+// Group ids and distinct rows (group.hip): BinaryRow's getters feeding a LinkedHashMap, null equal to null.
+int fury_row_group(const fury_schema* s, const int32_t* fields, int32_t num_keys, const void* rows,
+                   const int64_t* row_offsets, int64_t nrows, const uint32_t* hashes, int64_t* out_first,
+                   int64_t* out_group_ids, int64_t* out_group_rows, int64_t* out_num_groups, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_group");
+  int st = check_key_fields(f, s, fields, num_keys, nrows, "has no row fields to group by",
+                            "there is no route: group by a subset of the keys, then each group by the rest");
+  if (st) return st;
   if ((st = check_required(f, "out_first", out_first))) return st;
   if ((st = check_aligned(f, 8, {{"out_first", out_first}, {"out_group_ids", out_group_ids},
                                  {"out_group_rows", out_group_rows}, {"out_num_groups", out_num_groups}})))
@@ -1393,32 +1454,98 @@ int fury_row_group(const fury_schema* s, const int32_t* fields, int32_t num_keys
       return check_hip(hipMemsetAsync(out_num_groups, 0, 8, hs), "fury_row_group: memset");
     });
   }
-  if ((st = check_source(f, rows, row_offsets, rows_of(s), true, &a.side))) return st;
-  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}}))) return st;
-  a.side.nrows = nrows;
-  a.side.bitmap_bytes = s->bitmap_bytes;
-  a.side.fixed_size = s->fixed_size;
-  a.nkeys = num_keys;
-  a.hashes = hashes;
+  ProjArgs h{};
+  if ((st = group_batch_args(f, s, fields, num_keys, rows, row_offsets, nrows, hashes, &a, &h))) return st;
   a.out_first = out_first;
   a.out_group_ids = out_group_ids;
   a.out_group_rows = out_group_rows;
   a.out_num_groups = out_num_groups;
-  ProjArgs h{};                                   // the keys as fury_row_hash hashes them
-  h.ncols = num_keys;
-  h.bitmap_bytes = s->bitmap_bytes;
-  h.fixed_size = s->fixed_size;
-  h.nrows = nrows;
-  h.nt = 1;
-  for (int j = 0; j < num_keys; j++) {
-    const FieldPlan& p = s->plan[fields[j]];
-    const int32_t width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
-    a.key[j].left_slot = a.key[j].right_slot = fields[j];
-    a.key[j].kind = h.col[j].kind = p.kind;
-    a.key[j].width = h.col[j].width = width;
-    h.col[j].slot = fields[j];
-  }
   return launch_checked(hs, &a, [&] { return launch_group(a, &h, hs); });
+}
+
+// The slots of an index of nrows rows: group.hip's capacity.
+int64_t fury_row_index_slots(int64_t nrows) {
+  if (nrows < 0 || nrows > INT32_MAX) return -1;
+  return group_table_slots(nrows);
+}
+
+// The table of fury_row_group, kept (group.hip): HashMap.putIfAbsent of every row's key fields.
+int fury_row_index_build(const fury_schema* s, const int32_t* fields, int32_t num_keys, const void* rows,
+                         const int64_t* row_offsets, int64_t nrows, const uint32_t* hashes, uint64_t* table,
+                         int64_t table_slots, int64_t* out_first, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_index_build");
+  int st = check_key_fields(f, s, fields, num_keys, nrows, "has no row fields to index",
+                            "there is no route: index a subset of the keys and verify the rest with "
+                            "fury_row_keys_equal");
+  if (st) return st;
+  if ((st = check_required(f, "table", table))) return st;
+  if ((st = check_aligned(f, 8, {{"table", table}, {"out_first", out_first}}))) return st;
+  if ((st = check_aligned(f, 4, {{"hashes", hashes}}))) return st;
+  if (nrows > INT32_MAX) return invalid(f, "batch too large");
+  if (table_slots != fury_row_index_slots(nrows))
+    return invalid(f, "table_slots " + std::to_string(table_slots) + " is not fury_row_index_slots(" +
+                          std::to_string(nrows) + ") = " + std::to_string(fury_row_index_slots(nrows)));
+  GroupArgs a{};
+  ProjArgs h{};
+  if (nrows > 0) {
+    if ((st = group_batch_args(f, s, fields, num_keys, rows, row_offsets, nrows, hashes, &a, &h))) return st;
+    a.out_first = out_first;
+  }
+  return launch_checked(hs, &a, [&] { return launch_index_build(a, &h, table, table_slots, hs); });
+}
+
+// The probe of a hash join (lookup.hip): HashMap.get with every probe row's key fields.
+int fury_row_lookup(const fury_key_side* probe, const fury_key_side* build, int32_t num_keys,
+                    const uint64_t* table, int64_t table_slots, const uint32_t* probe_hashes, int32_t flags,
+                    int64_t* out_rows, uint32_t* out_mask, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_lookup");
+  int st = check_required(f, "probe", probe);
+  if (st) return st;
+  if ((st = check_required(f, "build", build))) return st;
+  const fury_key_side* sides[2] = {probe, build};
+  const std::string names[2] = {f + ": probe", f + ": build"};
+  if ((st = check_key_sides(f, sides, names, "probe", "build", num_keys))) return st;
+  for (int s = 0; s < 2; s++)
+    if (sides[s]->indices) return invalid(names[s], "indices must be null: the call takes whole batches");
+  if ((st = check_required(f, "table", table))) return st;
+  if (build->nrows > INT32_MAX) return invalid(names[1], "batch too large");
+  if (table_slots != fury_row_index_slots(build->nrows))
+    return invalid(f, "table_slots " + std::to_string(table_slots) + " is not fury_row_index_slots(" +
+                          std::to_string(build->nrows) + ") = " +
+                          std::to_string(fury_row_index_slots(build->nrows)));
+  if (flags & ~FURY_KEYS_NULL_EQUAL) return invalid(f, "unknown flags " + std::to_string(flags));
+  if (!out_rows && !out_mask) return invalid(f, "out_rows and out_mask are both null");
+  if ((st = check_aligned(f, 8, {{"table", table}, {"out_rows", out_rows}}))) return st;
+  if ((st = check_aligned(f, 4, {{"probe_hashes", probe_hashes}, {"out_mask", out_mask}}))) return st;
+  for (int s = 0; s < 2; s++)
+    if ((st = check_aligned(names[s], 8, {{"row_offsets", sides[s]->row_offsets}}))) return st;
+  if (probe->nrows == 0) return FURY_OK;
+  if ((probe->nrows + 255) / 256 > INT32_MAX) return invalid(names[0], "batch too large");
+  LookupArgs a{};
+  for (int s = 0; s < 2; s++) {
+    const fury_schema* sc = sides[s]->schema;
+    // an empty build batch has no rows and no offsets to read: every probe row finds nothing
+    const bool any = sides[s]->nrows > 0;
+    if ((st = check_source(names[s], sides[s]->rows, sides[s]->row_offsets, any ? rows_of(sc) : kFixedRows, any,
+                           &a.side[s])))
+      return st;
+    a.side[s].nrows = sides[s]->nrows;
+    a.side[s].bitmap_bytes = sc->bitmap_bytes;
+    a.side[s].fixed_size = sc->fixed_size;
+  }
+  a.nkeys = num_keys;
+  a.flags = flags;
+  a.table = table;
+  a.cap = static_cast<uint64_t>(table_slots);
+  a.hashes = probe_hashes;
+  a.out_rows = out_rows;
+  a.out_mask = out_mask;
+  fill_key_recs(probe, build, num_keys, a.key);
+  ProjArgs h{};
+  hash_key_args(probe->schema, probe->fields, num_keys, probe->nrows, &h);
+  return launch_checked(hs, &a, [&] { return launch_lookup(a, &h, hs); });
 }
 
 // H of rule 1 on the host: a CPU worker routes a lookup key to the partition the device chose.

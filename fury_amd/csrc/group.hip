@@ -44,6 +44,9 @@
 // hashes (a caller's mistake) may end in two groups, nothing else.
 // Bounds follow "Decode bounds" in kernels.h (row_ok / slot_count / span_ok) as hash.hip applies
 // them; all address arithmetic is int64.
+// fury_row_index_build (launch_index_build) is the same table kept: the caller's memory instead of
+// workspace, the same hash, memset and probe (build_table), the slot indices and resolve only when
+// out_first is wanted.  lookup.hip reads that table after the kernel boundary, as resolve does.
 #include <hip/hip_runtime.h>
 
 #include "keys_dev.h"
@@ -53,47 +56,11 @@ namespace fury {
 namespace {
 
 constexpr int kGroupThreads = 256;
-constexpr uint64_t kEmpty = ~uint64_t(0);
-// The slot index recorded for a row that is in no slot.  Never probed either: at capacity 2^32 the
-// last slot stays empty, so the value is unambiguous.
-constexpr uint32_t kNoSlot = 0xffffffffu;
 
 __device__ __forceinline__ CKeyRec* keys_of(const GroupArgs& a) { return (CKeyRec*)(a.key); }
 
 __device__ __forceinline__ int64_t row_base(const GroupArgs& a, int64_t r) {
   return a.side.row_offsets ? gl(a.side.row_offsets)[r] : r * a.side.fixed_size;
-}
-
-// Rule 5 for the lane's own row: every non-null STRING / BINARY / DECIMAL key value lies inside the
-// batch.  The header is inside it (row_ok).
-__device__ __forceinline__ bool own_keys_ok(const PairRow& me, CKeyRec* key, int nkeys) {
-  bool ok = true;
-  for (int k0 = 0; k0 < nkeys; k0 += kKeyGroup) {
-    uint64_t bits[kKeyGroup], slot[kKeyGroup];
-#pragma unroll
-    for (int u = 0; u < kKeyGroup; u++) {
-      bits[u] = ~uint64_t(0);
-      slot[u] = 0;
-      if (k0 + u < nkeys) {
-        const int32_t f = key[k0 + u].left_slot;
-        const uint8_t* hdr = me.rows + me.base;
-        bits[u] = load8(hdr + 8 * static_cast<int64_t>(f >> 6));
-        slot[u] = load8(hdr + me.bitmap_bytes + 8 * static_cast<int64_t>(f));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kKeyGroup; u++) {
-      if (k0 + u >= nkeys) break;
-      CKeyRec& c = key[k0 + u];
-      const bool isnull = (bits[u] >> (c.left_slot & 63)) & 1;
-      if (c.kind >= kBytes && !isnull) {
-        bool bad = false;
-        (void)slot_count(c.kind, c.width, slot[u], me.base, me.rows, me.total, &bad);
-        ok = ok && !bad;
-      }
-    }
-  }
-  return ok;
 }
 
 // VAR: some key is STRING / BINARY / DECIMAL.
@@ -117,7 +84,10 @@ __global__ __launch_bounds__(kGroupThreads) void group_probe(GroupArgs a, const 
   }
   pr[0].base = row_base(a, i);
   bool ok = row_ok(pr[0].base, a.side.fixed_size, total);
-  if (VAR && ok) ok = own_keys_ok(pr[0], keys_of(a), a.nkeys);
+  if (VAR && ok) {
+    bool any_null = false;                        // of no interest here: null equals null
+    ok = own_keys_ok<true>(pr[0], keys_of(a), a.nkeys, any_null);
+  }
   uint32_t found = kNoSlot;
   if (ok) {
     const uint64_t mine = (static_cast<uint64_t>(h) << 32) | static_cast<uint64_t>(i);
@@ -145,7 +115,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_probe(GroupArgs a, const 
     }
   }
   if (found == kNoSlot) raise_oob(a.err, i);
-  gl(slot_of)[i] = found;
+  if (slot_of) gl(slot_of)[i] = found;           // fury_row_index_build without out_first: not wanted
 }
 
 __global__ __launch_bounds__(kGroupThreads) void group_resolve(int64_t n, const uint64_t* __restrict__ table,
@@ -192,25 +162,16 @@ int64_t group_workspace_bytes(int64_t nrows, bool own_hashes, bool numbered) {
   return words * 8 + ((nrows + 1) / 2) * 8 * (own_hashes ? 2 : 1);
 }
 
-int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stream) {
+namespace {
+
+// What launch_group and launch_index_build share: the keys hashed into `own` when the caller gave no
+// hashes, every slot of `table` EMPTY, then the probe; slot_of NULL: the slot indices are not wanted.
+int build_table(const GroupArgs& a, const ProjArgs* hash_args, uint32_t* own, uint64_t* table, int64_t cap,
+                uint32_t* slot_of, hipStream_t stream) {
   const int64_t n = a.side.nrows;
-  if (n == 0) return FURY_OK;
-  if (n > 0x7fffffff) return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
-  const bool numbered = a.out_group_ids || a.out_group_rows || a.out_num_groups;
-  const bool own_hashes = a.hashes == nullptr;
-  const int64_t cap = group_table_slots(n);
-  // [table x cap][scan x n][count][scan scratch][slot_of x n (uint32)][hashes x n (uint32)]
-  DevBlock ws;
-  int st = ws.alloc(group_workspace_bytes(n, own_hashes, numbered), stream);
-  if (st) return st;
-  uint64_t* table = ws.as<uint64_t>();
-  int64_t* scan = reinterpret_cast<int64_t*>(table + cap);
-  int64_t* count = scan + n;
-  int64_t* sws = count + 1;
-  uint32_t* slot_of = reinterpret_cast<uint32_t*>(numbered ? sws + scan_workspace(n) : scan);
-  uint32_t* own = slot_of + ((n + 1) / 2) * 2;
   const uint32_t* hashes = a.hashes;
-  if (own_hashes) {
+  int st;
+  if (!hashes) {
     ProjArgs h = *hash_args;
     h.err = a.err;
     st = launch_hash(h, a.side.rows, a.side.row_offsets, 0, 1, own, nullptr, stream);
@@ -229,6 +190,30 @@ int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stre
     hipLaunchKernelGGL(group_probe<false>, grid, block, 0, stream, a, hashes, table,
                        static_cast<uint64_t>(cap), slot_of);
   }
+  return FURY_OK;
+}
+
+}  // namespace
+
+int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stream) {
+  const int64_t n = a.side.nrows;
+  if (n == 0) return FURY_OK;
+  if (n > 0x7fffffff) return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
+  const bool numbered = a.out_group_ids || a.out_group_rows || a.out_num_groups;
+  const bool own_hashes = a.hashes == nullptr;
+  const int64_t cap = group_table_slots(n);
+  // [table x cap][scan x n][count][scan scratch][slot_of x n (uint32)][hashes x n (uint32)]
+  DevBlock ws;
+  int st = ws.alloc(group_workspace_bytes(n, own_hashes, numbered), stream);
+  if (st) return st;
+  uint64_t* table = ws.as<uint64_t>();
+  int64_t* scan = reinterpret_cast<int64_t*>(table + cap);
+  int64_t* count = scan + n;
+  int64_t* sws = count + 1;
+  uint32_t* slot_of = reinterpret_cast<uint32_t*>(numbered ? sws + scan_workspace(n) : scan);
+  uint32_t* own = slot_of + ((n + 1) / 2) * 2;
+  if ((st = build_table(a, hash_args, own, table, cap, slot_of, stream))) return st;
+  const dim3 grid(static_cast<unsigned>((n + kGroupThreads - 1) / kGroupThreads)), block(kGroupThreads);
   hipLaunchKernelGGL(group_resolve, grid, block, 0, stream, n, table, slot_of, a.out_first,
                      numbered ? scan : nullptr);
   if (numbered) {
@@ -237,6 +222,32 @@ int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stre
                        a.out_group_ids, a.out_group_rows, a.out_num_groups);
   }
   return check_hip(hipGetLastError(), "group launch");
+}
+
+int launch_index_build(const GroupArgs& a, const ProjArgs* hash_args, uint64_t* table, int64_t cap,
+                       hipStream_t stream) {
+  const int64_t n = a.side.nrows;
+  if (n > 0x7fffffff) return set_error(FURY_ERR_INVALID_ARGUMENT, "batch too large");
+  if (n == 0)                                     // the two slots of an empty index
+    return check_hip(hipMemsetAsync(table, 0xff, static_cast<size_t>(cap) * 8, stream), "index build: memset");
+  const bool own_hashes = a.hashes == nullptr, resolve = a.out_first != nullptr;
+  // [slot_of x n (uint32), when out_first is wanted][hashes x n (uint32), when the call hashes]
+  DevBlock ws;
+  const int64_t per = ((n + 1) / 2) * 2;
+  if (own_hashes || resolve) {
+    const int st = ws.alloc(per * 4 * ((own_hashes ? 1 : 0) + (resolve ? 1 : 0)), stream);
+    if (st) return st;
+  }
+  uint32_t* slot_of = resolve ? ws.as<uint32_t>() : nullptr;
+  uint32_t* own = own_hashes ? ws.as<uint32_t>() + (resolve ? per : 0) : nullptr;
+  const int st = build_table(a, hash_args, own, table, cap, slot_of, stream);
+  if (st) return st;
+  if (resolve) {
+    const dim3 grid(static_cast<unsigned>((n + kGroupThreads - 1) / kGroupThreads)), block(kGroupThreads);
+    hipLaunchKernelGGL(group_resolve, grid, block, 0, stream, n, table, slot_of, a.out_first,
+                       static_cast<int64_t*>(nullptr));
+  }
+  return check_hip(hipGetLastError(), "index build launch");
 }
 
 }  // namespace fury

@@ -496,6 +496,35 @@ int64_t group_table_slots(int64_t nrows);       // the smallest power of two >= 
 int64_t group_workspace_bytes(int64_t nrows, bool own_hashes, bool numbered);
 // FURY_ERR_INVALID_ARGUMENT ("batch too large") for nrows > 2^31 - 1: a slot holds 32 bits of row.
 int launch_group(const GroupArgs& a, const ProjArgs* hash_args, hipStream_t stream);
+// fury_row_index_build: launch_group's table, built by the same kernel, in the caller's `table` of
+// `cap` == group_table_slots(nrows) slots; a.out_first optional (group_resolve), the other outputs
+// unused.  nrows == 0 marks the slots empty.  Workspace: 4 bytes per row for the call's own hashes, 4
+// per row of slot indices when out_first is given.
+int launch_index_build(const GroupArgs& a, const ProjArgs* hash_args, uint64_t* table, int64_t cap,
+                       hipStream_t stream);
+
+// ---- hash-join probe against a built index: lookup.hip ---------------------------------------------------
+// Probe row j (side[0], keys key[k].left_slot) against the rows of side[1] that `table` names (keys
+// key[k].right_slot): out_rows[j] = the row of the first slot on j's walk whose hash half equals
+// hashes[j] and whose row's keys equal j's under rule 2 of fury_row_keys_equal with `flags`, else -1;
+// bit j of out_mask = out_rows[j] >= 0 (whole words, tail bits zero); either may be NULL.  The table
+// is read, never written, and nothing in it is trusted: the rules are numbered in include/fury_row.h.
+// hashes: side[0].nrows entries or NULL (launch_hash of hash_args, seed 0, into workspace).
+// side[].indices unused.  Asynchronous on `stream`.
+struct LookupArgs {
+  KeySide side[2];                    // [0] the probe batch, [1] the build batch
+  KeyRec key[kMaxEqualKeys];
+  int32_t nkeys;
+  int32_t flags;                      // FURY_KEYS_NULL_EQUAL
+  const uint64_t* table;
+  uint64_t cap;                       // group_table_slots(side[1].nrows)
+  const uint32_t* hashes;
+  int64_t* out_rows;
+  uint32_t* out_mask;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(LookupArgs) <= 4096, "LookupArgs must fit the kernel argument block");
+int launch_lookup(const LookupArgs& a, const ProjArgs* hash_args, hipStream_t stream);
 
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each

@@ -1,6 +1,7 @@
 // keys_dev.h -- the comparison of two rows' key fields, shared by the kernels that decide key
 // equality from the row bytes (keys_equal.hip: pairs of two batches; group.hip: a row against the
-// representative of a hash-table slot).  One implementation of rule 2 of fury_row_keys_equal: header
+// representative of a hash-table slot; lookup.hip: a probe row against the build row of a slot), and
+// the check of a lane's own keys that the two table kernels make first.  One implementation of rule 2 of fury_row_keys_equal: header
 // words in flight, slot_count, same_bytes and the tail rule.  Design notes: keys_equal.hip.
 #pragma once
 
@@ -71,6 +72,49 @@ struct PairRow {
   int32_t bitmap_bytes;
   bool ok;                            // index in [0, nrows) and header inside the batch
 };
+
+// A hash-table word of group.hip / lookup.hip: (hash << 32) | row.  A real entry has row < 2^31, so it
+// never equals kEmpty even with hash 0xFFFFFFFF.
+constexpr uint64_t kEmpty = ~uint64_t(0);
+// The slot index recorded for a row that is in no slot.  Never probed either: at capacity 2^32 the
+// last slot stays empty, so the value is unambiguous.
+constexpr uint32_t kNoSlot = 0xffffffffu;
+
+// Rule 5 for a lane's own row `me` (its header is inside the batch: row_ok), keys read at
+// key[k].left_slot: every non-null STRING / BINARY / DECIMAL key value lies inside the batch.
+// `any_null` is set (never cleared) when a key is null.  VAR = false reads no slot words: no key has a
+// span to check, only the null bits are looked at.
+template <bool VAR>
+__device__ __forceinline__ bool own_keys_ok(const PairRow& me, CKeyRec* key, int nkeys, bool& any_null) {
+  bool ok = true;
+  for (int k0 = 0; k0 < nkeys; k0 += kKeyGroup) {
+    uint64_t bits[kKeyGroup], slot[kKeyGroup];
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {
+      bits[u] = ~uint64_t(0);
+      slot[u] = 0;
+      if (k0 + u < nkeys) {
+        const int32_t f = key[k0 + u].left_slot;
+        const uint8_t* hdr = me.rows + me.base;
+        bits[u] = load8(hdr + 8 * static_cast<int64_t>(f >> 6));
+        if (VAR) slot[u] = load8(hdr + me.bitmap_bytes + 8 * static_cast<int64_t>(f));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {
+      if (k0 + u >= nkeys) break;
+      CKeyRec& c = key[k0 + u];
+      const bool isnull = (bits[u] >> (c.left_slot & 63)) & 1;
+      any_null = any_null || isnull;
+      if (VAR && c.kind >= kBytes && !isnull) {
+        bool bad = false;
+        (void)slot_count(c.kind, c.width, slot[u], me.base, me.rows, me.total, &bad);
+        ok = ok && !bad;
+      }
+    }
+  }
+  return ok;
+}
 
 // Every key position of the pair pr[0] / pr[1] equal under rule 2 (key[k].left_slot of pr[0] against
 // key[k].right_slot of pr[1]).  Every key is examined for its null bit and bounds whatever the

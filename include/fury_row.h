@@ -595,6 +595,87 @@ int fury_row_group(const fury_schema* schema, const int32_t* fields, int32_t num
                    int64_t* out_num_groups,     /* device, 1 entry, optional */
                    void* stream);
 
+/* Key index and lookup -- the probe side of a hash join: for every row of a probe batch, is its key
+ * present in a build batch, and at which row?  The batch form of HashMap.putIfAbsent(key fields, row)
+ * over the build batch (fury_row_index_build) followed by HashMap.get(key fields) for every probe row
+ * (fury_row_lookup), the key fields read with BinaryRow's getters, answered from the row bytes with
+ * nothing decoded.  One index serves any number of lookups: a dimension join, a semi-join or anti-join
+ * (IN / NOT IN), an upsert, a build side probed by a stream of batches.  The definition is normative;
+ * every output is a pure function of the two batches, the key fields and the flags:
+ *   1. Slots.  fury_row_index_slots(nrows) (host, no device work) = the smallest power of two that is at
+ *      least max(2, 2 * nrows): the number of 8-byte words of the table of a build batch of nrows rows.
+ *      It returns -1 for nrows < 0 or nrows > 2^31 - 1.
+ *   2. Build.  fury_row_index_build enters the rows of one batch into `table` (device, the caller's
+ *      memory, 8-byte aligned, required; table_slots words) exactly as fury_row_group builds its own
+ *      table: the same kernel, the equality of rule 1 of fury_row_group (null equals null), its rule 4
+ *      for `hashes` and its rule 5 for bounds.  A row that fails the bounds is never entered and raises
+ *      FURY_ERR_OUT_OF_BOUNDS on `stream` naming the row.  table_slots must equal
+ *      fury_row_index_slots(nrows), else FURY_ERR_INVALID_ARGUMENT.  out_first (device int64, nrows
+ *      entries, optional) receives what fury_row_group's out_first receives: the smallest row of row
+ *      i's group, its own number for a row that was not entered.  nrows == 0 marks the table's two
+ *      slots empty and writes nothing else.  Key types and the checks on `schema`, `fields` and
+ *      `num_keys` are those of fury_row_group (its rule 6); nrows > 2^31 - 1 is "batch too large".
+ *   3. The table.  Its contents are opaque: one slot per distinct key, holding the smallest entered row
+ *      of that key once the build has completed, but which slot a key lives in depends on how the
+ *      device scheduled the rows.  It is valid for lookups only with THIS batch, unmodified, THESE key
+ *      fields, the same hash function, and after the build has completed on its stream (a lookup on
+ *      the same stream is ordered behind it).
+ *   4. Lookup.  For probe row j, out_rows[j] (device int64, probe->nrows entries) = the smallest row i
+ *      of `build` that was entered into the table and whose key fields equal those of probe row j, or
+ *      -1 if there is none.  Equality is rule 2 of fury_row_keys_equal under `flags`
+ *      (FURY_KEYS_NULL_EQUAL or 0), probe->fields[k] compared with build->fields[k].  Bit j of
+ *      out_mask (device uint32 words, word j / 32, LSB first: the convention of fury_row_filter's
+ *      row_mask) = (out_rows[j] >= 0); all (probe->nrows + 31) / 32 words are written whole, the bits
+ *      at or past probe->nrows zero.  Either output may be NULL, not both.  With flags == 0 a probe
+ *      row with a null key matches nothing: it gets -1 without the table being walked, after its
+ *      bounds have been examined.  `indices` must be NULL on both sides (the call takes whole batches),
+ *      else FURY_ERR_INVALID_ARGUMENT.
+ *   5. Hashes.  probe_hashes == NULL: the call hashes the probe keys itself, as fury_row_hash does
+ *      with seed 0, into workspace; this pairs with a build whose `hashes` was NULL.  Otherwise
+ *      (device uint32, probe->nrows entries) the caller passes the same function of the key values
+ *      that the build got.  The hash only chooses where the walk starts and which slots are compared:
+ *      a mismatch between the two sides can only turn a match into -1, never produce a wrong match.
+ *   6. Probe-side bounds follow rule 5 of fury_row_keys_equal: a probe row whose header or key value
+ *      leaves its batch (or whose key size is negative) gets -1 and mask bit 0 whatever the flags, and
+ *      raises FURY_ERR_OUT_OF_BOUNDS on `stream` naming j.  Slots of fields that are not keys are never
+ *      looked at.
+ *   7. Table robustness.  The table is the caller's memory, so the lookup trusts none of it.  A slot on
+ *      row j's walk whose hash half equals j's hash and whose row half is >= build->nrows gives -1 for
+ *      j and raises FURY_ERR_OUT_OF_BOUNDS naming j; so does a named build row whose header or key
+ *      value leaves the build batch: the row is checked before any of its payload is read.  The walk
+ *      ends after at most table_slots steps, with -1.  For ANY table contents out_rows[j] is -1 or a
+ *      build row whose keys really equal those of probe row j, and nothing outside either batch or
+ *      the table's table_slots words is read.
+ *   8. Key types.  The two schemas need to share only the key types: rule 6 of fury_row_keys_equal,
+ *      same checks and messages (with "probe" and "build" for "left" and "right").
+ * fury_row_lookup: 1 <= num_keys <= 64.  `table` is required, 8-byte aligned, and table_slots must
+ * equal fury_row_index_slots(build->nrows), else FURY_ERR_INVALID_ARGUMENT; out_rows is 8-byte, out_mask
+ * and probe_hashes 4-byte aligned; `rows` and row_offsets follow fury_row_keys_equal.  A build batch of
+ * no rows may have rows == NULL and row_offsets == NULL: every probe row gets -1.  Unknown bits in
+ * `flags` return FURY_ERR_INVALID_ARGUMENT.  probe->nrows == 0 does nothing and returns FURY_OK.  Both calls are
+ * asynchronous on `stream` and never synchronise with the host; argument errors are returned before
+ * any device work.
+ * Workspace (stream-ordered, freed on `stream`): build: 4 bytes per row when the call hashes itself,
+ * plus 4 bytes per row when out_first is given; lookup: 4 bytes per probe row when the call hashes
+ * itself, else none.
+ * Limits: device memory only; at most 2^31 - 1 build rows; a value is compared by one lane however
+ * long it is, as in fury_row_keys_equal. */
+int64_t fury_row_index_slots(int64_t nrows);
+int fury_row_index_build(const fury_schema* schema, const int32_t* fields, int32_t num_keys,
+                         const void* rows, const int64_t* row_offsets, int64_t nrows,
+                         const uint32_t* hashes,      /* device, nrows entries, optional */
+                         uint64_t* table,             /* device, table_slots words, the caller's memory */
+                         int64_t table_slots,         /* fury_row_index_slots(nrows) */
+                         int64_t* out_first,          /* device, nrows entries, optional */
+                         void* stream);
+int fury_row_lookup(const fury_key_side* probe, const fury_key_side* build, int32_t num_keys,
+                    const uint64_t* table, int64_t table_slots,
+                    const uint32_t* probe_hashes,     /* device, probe->nrows entries, optional */
+                    int32_t flags,                    /* FURY_KEYS_NULL_EQUAL */
+                    int64_t* out_rows,                /* device, probe->nrows entries */
+                    uint32_t* out_mask,               /* device, (probe->nrows + 31) / 32 words */
+                    void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
