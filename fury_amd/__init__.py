@@ -11,7 +11,10 @@ _KEYS = ("KeySide", "keys_equal_into", "bind_keys_equal", "keys_equal", "candida
 _GROUP = ("Groups", "group_rows_into", "bind_group", "group_rows", "group_sizes", "distinct")
 _LOOKUP = ("KeyIndex", "index_slots", "build_index_into", "build_index", "lookup_into", "bind_lookup",
            "lookup", "semi_join", "lookup_join_pairs")
-__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP]
+_ORDER = ("order_flags", "compare_into", "bind_compare", "compare_rows", "order_words_into", "order_words",
+          "word_continues", "refine_order", "argsort_rows", "sort_rows", "is_sorted", "search_bounds",
+          "search_sorted")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP, *_ORDER]
 
 
 def __getattr__(name):
@@ -28,6 +31,9 @@ def __getattr__(name):
         import importlib                          # `from . import lookup` would ask for "lookup" here again
         module = importlib.import_module(".lookup", __name__)
         return module if name == "lookup" else getattr(module, name)      # the module is callable
+    if name in _ORDER:                            # fury_amd.order: the order of rows by key fields
+        import importlib
+        return getattr(importlib.import_module(".order", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -62,6 +62,8 @@ class FuryKeySide(ctypes.Structure):
 
 
 KEYS_NULL_EQUAL = 1
+ORDER_DESC = 1
+ORDER_NULLS_LAST = 2
 PARTITION_MAX_PARTS = 65535
 CONCAT_MAX_SOURCES = 32
 
@@ -115,6 +117,9 @@ SIGNATURES = {
                                             _P]),
     "fury_row_lookup": (ctypes.c_int, [ctypes.POINTER(FuryKeySide), ctypes.POINTER(FuryKeySide), _I32, _P,
                                        _I64, _P, _I32, _P, _P, _P]),
+    "fury_row_compare": (ctypes.c_int, [ctypes.POINTER(FuryKeySide), ctypes.POINTER(FuryKeySide), _I32,
+                                        ctypes.POINTER(_I32), _I64, _P, _P]),
+    "fury_row_order_words": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

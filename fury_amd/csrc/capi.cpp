@@ -1377,6 +1377,103 @@ int fury_row_keys_equal(const fury_key_side* left, const fury_key_side* right, i
   return launch_checked(hs, &a, [&] { return launch_keys_equal(a, hs); });
 }
 
+static int check_key_fields(const std::string& f, const fury_schema* s, const int32_t* fields, int32_t num_keys,
+                            int64_t nrows, const char* none, const char* route);
+
+// One key position of an ordering: field `left_field` (of the plan `p`) against `right_field`.
+static void fill_order_key(const FieldPlan& p, int32_t left_field, int32_t right_field, int32_t flags,
+                           OrderKey* v) {
+  v->left_slot = left_field;
+  v->right_slot = right_field;
+  v->kind = p.kind;
+  v->width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+  v->cls = (p.type_id == FURY_TYPE_FLOAT32 || p.type_id == FURY_TYPE_FLOAT64) ? kOrdFloat
+           : (p.kind == kBytes || p.kind == kBool)                            ? kOrdBytes
+                                                                              : kOrdSigned;
+  v->flags = flags;
+}
+
+// The order of row pairs (compare.hip): BinaryRow's getters on both rows, value against value, key after key.
+int fury_row_compare(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
+                     const int32_t* key_flags, int64_t num_pairs, int8_t* out_cmp, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_compare");
+  int st = check_required(f, "left", left);
+  if (st) return st;
+  if ((st = check_required(f, "right", right))) return st;
+  const fury_key_side* sides[2] = {left, right};
+  const std::string names[2] = {f + ": left", f + ": right"};
+  if ((st = check_key_sides(f, sides, names, "left", "right", num_keys))) return st;
+  if ((st = check_count(f, "num_pairs", num_pairs))) return st;
+  for (int s = 0; s < 2; s++)
+    if (!sides[s]->indices && sides[s]->nrows < num_pairs)
+      return invalid(names[s], "nrows " + std::to_string(sides[s]->nrows) + " < num_pairs " +
+                                   std::to_string(num_pairs) + " and there are no indices");
+  for (int j = 0; key_flags && j < num_keys; j++)
+    if (key_flags[j] & ~(FURY_ORDER_DESC | FURY_ORDER_NULLS_LAST))
+      return invalid(f, "key " + std::to_string(j) + ": unknown flags " + std::to_string(key_flags[j]));
+  if ((st = check_required(f, "out_cmp", out_cmp))) return st;
+  for (int s = 0; s < 2; s++)
+    if ((st = check_aligned(names[s], 8, {{"indices", sides[s]->indices},
+                                          {"row_offsets", sides[s]->row_offsets}})))
+      return st;
+  if (num_pairs == 0) return FURY_OK;
+  CompareArgs a{};
+  for (int s = 0; s < 2; s++) {
+    const fury_schema* sc = sides[s]->schema;
+    if ((st = check_source(names[s], sides[s]->rows, sides[s]->row_offsets, rows_of(sc), true, &a.side[s])))
+      return st;
+    a.side[s].nrows = sides[s]->nrows;
+    a.side[s].indices = sides[s]->indices;
+    a.side[s].bitmap_bytes = sc->bitmap_bytes;
+    a.side[s].fixed_size = sc->fixed_size;
+  }
+  if ((num_pairs + 255) / 256 > INT32_MAX) return invalid(f, "batch too large");
+  a.nkeys = num_keys;
+  a.num_pairs = num_pairs;
+  a.out_cmp = out_cmp;
+  for (int j = 0; j < num_keys; j++)
+    fill_order_key(left->schema->plan[left->fields[j]], left->fields[j], right->fields[j],
+                   key_flags ? key_flags[j] : 0, &a.key[j]);
+  return launch_checked(hs, &a, [&] { return launch_compare(a, hs); });
+}
+
+// Order words (order.hip): one chunk of one key field as integers whose order is fury_row_compare's.
+int fury_row_order_words(const fury_schema* s, int32_t field, int32_t flags, int32_t chunk, const void* rows,
+                         const int64_t* row_offsets, int64_t nrows, const int64_t* indices, int64_t num_out,
+                         int64_t* out_words, uint32_t* out_more, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_order_words");
+  int st = check_key_fields(f, s, &field, 1, nrows, "has no row fields to order by", "there is no route");
+  if (st) return st;
+  if (flags & ~(FURY_ORDER_DESC | FURY_ORDER_NULLS_LAST)) return invalid(f, "unknown flags " + std::to_string(flags));
+  if (chunk < 0) return invalid(f, "chunk < 0");
+  if ((st = check_count(f, "num_out", num_out))) return st;
+  if (!indices && nrows < num_out)
+    return invalid(f, "nrows " + std::to_string(nrows) + " < num_out " + std::to_string(num_out) +
+                          " and there are no indices");
+  if ((st = check_required(f, "out_words", out_words))) return st;
+  if ((st = check_aligned(f, 8, {{"out_words", out_words}, {"indices", indices}, {"row_offsets", row_offsets}})))
+    return st;
+  if ((st = check_aligned(f, 4, {{"out_more", out_more}}))) return st;
+  OrderWordsArgs a{};
+  if (num_out > 0) {
+    if ((st = check_source(f, rows, row_offsets, rows_of(s), true, &a.side))) return st;
+    if ((num_out + 255) / 256 > INT32_MAX) return invalid(f, "batch too large");
+  }
+  a.side.nrows = nrows;
+  a.side.indices = indices;
+  a.side.bitmap_bytes = s->bitmap_bytes;
+  a.side.fixed_size = s->fixed_size;
+  a.num_out = num_out;
+  a.chunk = chunk;
+  a.out_words = out_words;
+  a.out_more = out_more;
+  fill_order_key(s->plan[field], field, field, flags, &a.key);
+  if (num_out == 0 && !out_more) return FURY_OK;
+  return launch_checked(hs, &a, [&] { return launch_order_words(a, hs); });
+}
+
 // The key fields of one batch, as fury_row_group and fury_row_index_build check them: the selection, then
 // no LIST / STRUCT / MAP key.  `fields` stands in for the column table check_selection wants, as in
 // fury_row_hash.

@@ -526,6 +526,55 @@ struct LookupArgs {
 static_assert(sizeof(LookupArgs) <= 4096, "LookupArgs must fit the kernel argument block");
 int launch_lookup(const LookupArgs& a, const ProjArgs* hash_args, hipStream_t stream);
 
+// ---- the order of rows by key fields: compare.hip, order.hip ----------------------------------------------
+// One key position of an ordering: KeyRec's members and what the order needs beyond equality, how the
+// value bytes rank (`cls`) and the position's FURY_ORDER_* flags.  A record of its own: KeyRec and the
+// argument blocks of the equality kernels stay as they are.  Indexed wave-uniformly (scalar loads).
+enum OrderClass : int32_t {
+  kOrdSigned = 0,                     // kFixed: two's complement at `width`; kDecimal: 128-bit
+  kOrdFloat = 1,                      // kFixed, width 4 / 8: IEEE-754 totalOrder of the raw bits
+  kOrdBytes = 2                       // kBytes: unsigned bytes, a prefix first; kBool: 0 / 1
+};
+struct OrderKey {
+  int32_t left_slot;                  // field index in the left schema (order_words: the field)
+  int32_t right_slot;                 // ... in the right one
+  int32_t kind;                       // FieldKind: kFixed / kBool / kBytes / kDecimal
+  int32_t width;                      // kFixed: 1 / 2 / 4 / 8; kBool: 1; kDecimal: 16
+  int32_t cls;                        // OrderClass
+  int32_t flags;                      // FURY_ORDER_DESC | FURY_ORDER_NULLS_LAST
+};
+// Pair j as launch_keys_equal defines it; out_cmp[j] = -1 / 0 / +1 under the order rules numbered in
+// include/fury_row.h.  Bounds = "Decode bounds" above per side: an index outside [0, nrows) or a row
+// that fails row_ok has every key null, a key value that fails span_ok is null, each raises kErrBounds
+// with j, and the result is the rules' with those nulls.  Asynchronous on `stream`, no workspace.
+struct CompareArgs {
+  KeySide side[2];
+  OrderKey key[kMaxEqualKeys];
+  int64_t num_pairs;
+  int32_t nkeys;
+  int32_t pad_;
+  int8_t* out_cmp;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(CompareArgs) <= 4096, "CompareArgs must fit the kernel argument block");
+// FURY_ERR_INVALID_ARGUMENT ("batch too large") for a pair count the grid cannot index.
+int launch_compare(const CompareArgs& a, hipStream_t stream);
+// out_words[j] = the order word of chunk `chunk` of key.left_slot of row side.indices[j] (NULL: j),
+// as fury_row_order_words defines it; *out_more (optional; zeroed on the stream by the launcher) = 1
+// when any output row's value continues past the chunk.  Bounds as launch_compare, raising with j.
+// Asynchronous on `stream`, no workspace.
+struct OrderWordsArgs {
+  KeySide side;
+  OrderKey key;
+  int64_t num_out;
+  int32_t chunk;
+  int32_t pad_;
+  int64_t* out_words;
+  uint32_t* out_more;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+int launch_order_words(const OrderWordsArgs& a, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

@@ -3,6 +3,8 @@
 // representative of a hash-table slot; lookup.hip: a probe row against the build row of a slot), and
 // the check of a lane's own keys that the two table kernels make first.  One implementation of rule 2 of fury_row_keys_equal: header
 // words in flight, slot_count, same_bytes and the tail rule.  Design notes: keys_equal.hip.
+// Below it the order of two rows' key fields (compare.hip) and the pieces order.hip shares with it: one
+// implementation of rules 1-4 of fury_row_compare, pair_keys_compare beside pair_keys_equal.
 #pragma once
 
 #include "project_dev.h"
@@ -181,6 +183,135 @@ __device__ __forceinline__ bool pair_keys_equal(const PairRow (&pr)[2], CKeyRec*
     }
   }
   return eq;
+}
+
+// ---- the order of two rows' key fields (compare.hip, order.hip): rules of fury_row_compare ----------------
+using COrderKey = __attribute__((address_space(4))) const OrderKey;
+
+// A kFixed slot's `width` value bytes as an unsigned integer that ranks as rule 3 does: two's
+// complement with the sign bit flipped; a float with the usual total-order transform (negative: all
+// bits flipped, else the sign bit set).
+__device__ __forceinline__ uint64_t order_fixed(uint64_t slot, int width, int cls) {
+  const uint64_t mask = ~uint64_t(0) >> (64 - 8 * width);
+  const uint64_t sign = uint64_t(1) << (8 * width - 1);
+  const uint64_t v = slot & mask;
+  if (cls == kOrdFloat && (v & sign)) return ~v & mask;
+  return v ^ sign;
+}
+
+// -1 / 0 / +1 of two words whose memory bytes rank lexicographically: the first byte in memory is the
+// low byte of the word, so the bytes are swapped and the words compared unsigned.
+__device__ __forceinline__ int order_word_cmp(uint64_t x, uint64_t y) {
+  const uint64_t bx = __builtin_bswap64(x), by = __builtin_bswap64(y);
+  return bx < by ? -1 : bx > by ? 1 : 0;
+}
+
+// Batch bytes [pl, pl + nl) of the left batch against [pr, pr + nr) of the right one, unsigned
+// lexicographic, a proper prefix first; both spans lie inside their batches (slot_count).  The first
+// differing 8-byte word decides; the tail is masked and the lengths break a tie.
+__device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_t tl, int64_t nl,
+                                           const uint8_t* rr, int64_t pr, int64_t tr, int64_t nr) {
+  const bool al = ((pl | pr) & 7) == 0;           // every well-formed row: aligned 8-byte loads
+  const int64_t n = nl < nr ? nl : nr;
+  const int64_t nw = n >> 3;
+  for (int64_t w0 = 0; w0 < nw; w0 += kPayWords) {
+    uint64_t x[kPayWords], y[kPayWords];
+#pragma unroll
+    for (int u = 0; u < kPayWords; u++) {
+      x[u] = y[u] = 0;
+      if (w0 + u < nw) {
+        x[u] = pay_word(rl, pl + 8 * (w0 + u), tl, al);
+        y[u] = pay_word(rr, pr + 8 * (w0 + u), tr, al);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPayWords; u++)
+      if (x[u] != y[u]) return order_word_cmp(x[u], y[u]);
+  }
+  const int rem = static_cast<int>(n & 7);
+  if (rem) {
+    const int c = order_word_cmp(pay_tail(rl, pl + 8 * nw, rem, tl, al), pay_tail(rr, pr + 8 * nw, rem, tr, al));
+    if (c) return c;
+  }
+  return nl < nr ? -1 : nl > nr ? 1 : 0;
+}
+
+// The order of the pair pr[0] / pr[1] over the key positions (key[k].left_slot of pr[0] against
+// key[k].right_slot of pr[1]): -1 / 0 / +1, the first position that differs decides.  As in
+// pair_keys_equal every key is examined for its null bit and bounds whatever the earlier keys gave,
+// `fail` is set (never cleared) when a value's span leaves its batch, and a side that is not ok has
+// every key null; here a failed value simply ranks as a null, so the result stays a total preorder.
+// Payloads are read only while the pair is undecided.  `key` is indexed wave-uniformly.
+template <bool VAR>
+__device__ __forceinline__ int pair_keys_compare(const PairRow (&pr)[2], COrderKey* key, int nkeys,
+                                                 bool& fail) {
+  int res = 0;
+  for (int k0 = 0; k0 < nkeys; k0 += kKeyGroup) {
+    uint64_t bits[kKeyGroup][2], slot[kKeyGroup][2];
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {         // every header word of the group, both sides
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        bits[u][s] = ~uint64_t(0);                // a row that cannot be read: every key null
+        slot[u][s] = 0;
+        if (k0 + u < nkeys && pr[s].ok) {
+          COrderKey& c = key[k0 + u];
+          const int32_t f = s == 0 ? c.left_slot : c.right_slot;
+          const uint8_t* hdr = pr[s].rows + pr[s].base;
+          bits[u][s] = load8(hdr + 8 * static_cast<int64_t>(f >> 6));
+          slot[u][s] = load8(hdr + pr[s].bitmap_bytes + 8 * static_cast<int64_t>(f));
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kKeyGroup; u++) {
+      if (k0 + u >= nkeys) break;
+      COrderKey& c = key[k0 + u];
+      const int kind = c.kind, width = c.width, flags = c.flags;
+      bool isnull[2];
+      int64_t n[2];
+#pragma unroll
+      for (int s = 0; s < 2; s++) {
+        const int32_t f = s == 0 ? c.left_slot : c.right_slot;
+        isnull[s] = (bits[u][s] >> (f & 63)) & 1;
+        n[s] = width;
+        if (VAR && kind >= kBytes && !isnull[s]) {
+          bool bad = false;
+          n[s] = slot_count(kind, width, slot[u][s], pr[s].base, pr[s].rows, pr[s].total, &bad);
+          if (bad) {
+            fail = true;
+            isnull[s] = true;
+          }
+        }
+      }
+      if (res != 0) continue;                     // decided: only the null bits and bounds above
+      int c3 = 0;                                 // rule 3, ascending
+      if (isnull[0] || isnull[1]) {               // rule 2: absolute, DESC does not flip it
+        if (isnull[0] != isnull[1]) res = (isnull[0] != ((flags & FURY_ORDER_NULLS_LAST) != 0)) ? -1 : 1;
+        continue;
+      } else if (VAR && kind == kBytes) {
+        c3 = order_bytes(pr[0].rows, pr[0].base + static_cast<int32_t>(slot[u][0] >> 32), pr[0].total, n[0],
+                         pr[1].rows, pr[1].base + static_cast<int32_t>(slot[u][1] >> 32), pr[1].total, n[1]);
+      } else if (VAR && kind == kDecimal) {       // 16 bytes, little-endian two's complement
+        const int64_t pl = pr[0].base + static_cast<int32_t>(slot[u][0] >> 32);
+        const int64_t pq = pr[1].base + static_cast<int32_t>(slot[u][1] >> 32);
+        const bool al = ((pl | pq) & 7) == 0;
+        const uint64_t lo0 = pay_word(pr[0].rows, pl, pr[0].total, al);
+        const uint64_t hi0 = pay_word(pr[0].rows, pl + 8, pr[0].total, al);
+        const uint64_t lo1 = pay_word(pr[1].rows, pq, pr[1].total, al);
+        const uint64_t hi1 = pay_word(pr[1].rows, pq + 8, pr[1].total, al);
+        const uint64_t h0 = hi0 ^ (uint64_t(1) << 63), h1 = hi1 ^ (uint64_t(1) << 63);
+        c3 = h0 != h1 ? (h0 < h1 ? -1 : 1) : lo0 < lo1 ? -1 : lo0 > lo1 ? 1 : 0;
+      } else if (kind == kBool) {
+        c3 = static_cast<int>((slot[u][0] & 0xff) != 0) - static_cast<int>((slot[u][1] & 0xff) != 0);
+      } else {                                    // kFixed
+        const uint64_t x = order_fixed(slot[u][0], width, c.cls), y = order_fixed(slot[u][1], width, c.cls);
+        c3 = x < y ? -1 : x > y ? 1 : 0;
+      }
+      res = (flags & FURY_ORDER_DESC) ? -c3 : c3;
+    }
+  }
+  return res;
 }
 
 }  // namespace

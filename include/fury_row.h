@@ -676,6 +676,83 @@ int fury_row_lookup(const fury_key_side* probe, const fury_key_side* build, int3
                     uint32_t* out_mask,               /* device, (probe->nrows + 31) / 32 words */
                     void* stream);
 
+/* The order of rows -- ORDER BY, top-k, a sortedness check, a binary search (range partitioning, merge
+ * joins), sorted runs: which of two rows' key fields is smaller?  The batch form of reading both rows'
+ * key fields with BinaryRow's getters and comparing the values key after key, answered from the row
+ * bytes with nothing decoded.  The reference ships no comparator of rows; the order below is this
+ * library's and is normative, so that a worker in any language orders rows as the device does:
+ *   1. Keys.  Pair j is pair j of fury_row_keys_equal (rule 1 there: rows left.indices[j] / right.indices[j],
+ *      or row j).  The rows are compared key position by key position, left.fields[k] against
+ *      right.fields[k]; the first position that differs decides, and the result is -1 (the left row
+ *      sorts first), 0 or +1.
+ *   2. Nulls.  Null against null is equal.  Null against a value: the null is smaller, or greater when
+ *      the position has FURY_ORDER_NULLS_LAST.  The placement is absolute: FURY_ORDER_DESC does not
+ *      flip it.
+ *   3. Value order, ascending.  BOOL: false < true, any non-zero stored byte being true.  INT8 / INT16 /
+ *      INT32 / INT64 / DATE32 / TIMESTAMP: signed at their width (a slot is zero-extended, so the sign
+ *      is taken at the width).  FLOAT32 / FLOAT64: IEEE-754 totalOrder of the raw bits: negative NaNs <
+ *      -inf < ... < -0.0 < +0.0 < ... < +inf < positive NaNs, NaNs ordered by payload.  This is not
+ *      Double.compare, which collapses the NaNs; it is chosen so that rule 5 holds.  DECIMAL: the 16
+ *      value bytes as a signed little-endian 128-bit integer (what Arrow's decimal128 and
+ *      BinaryWriter.writeDecimal store); the schema carries no scale, so equal scales are the
+ *      caller's business.  STRING / BINARY: unsigned byte-wise lexicographic, a proper prefix smaller.
+ *      For valid UTF-8 this is Unicode code-point order, NOT String.compareTo's UTF-16 code-unit order:
+ *      the two differ for supplementary characters against U+E000..U+FFFF.
+ *   4. Direction.  FURY_ORDER_DESC reverses rule 3 for that key position only.
+ *   5. Consistency.  For a pair without a bounds failure the result is 0 if and only if
+ *      fury_row_keys_equal with FURY_KEYS_NULL_EQUAL says equal: -0.0 and +0.0 differ, two NaNs are
+ *      equal iff their bits are, null differs from the empty string.
+ *   6. Bounds are the "Decode bounds" as fury_row_hash applies them, per side against that side's own
+ *      batch.  An index outside [0, nrows) or a row whose header leaves the batch makes every key of
+ *      that row null; a key value whose span leaves the batch or whose size is negative is null.  Each
+ *      such failure raises FURY_ERR_OUT_OF_BOUNDS on `stream` (fury_device_status) naming the pair (or
+ *      output) number j.  The result is still defined, by rules 1-4 with those nulls, and still a total
+ *      preorder, so a sort of a corrupt batch terminates and is deterministic.  All keys of a pair are
+ *      examined for null bits and bounds whatever the earlier keys gave, as in fury_row_keys_equal.
+ *      Nothing outside either batch is read, and slots of fields that are not keys are never looked at.
+ * Key types, the key count (1..64), the checks on each side's `schema` and `fields`, the equal type_id
+ * at every key position and their error codes are fury_row_keys_equal's.  key_flags: a host array of
+ * num_keys entries, each a combination of FURY_ORDER_DESC and FURY_ORDER_NULLS_LAST; NULL: all zeros
+ * (ascending, nulls first).  Unknown bits return FURY_ERR_INVALID_ARGUMENT.
+ *
+ * fury_row_compare: out_cmp[j] (device int8, num_pairs entries, required) = -1 / 0 / +1 for pair j.
+ * num_pairs == 0 returns FURY_OK and does nothing.  The call is asynchronous on `stream`, never
+ * synchronises with the host and allocates no workspace.
+ *
+ * fury_row_order_words: the piece that lets an integer sort order rows.  NK(value), the normalised key
+ * bytes, is a byte string whose unsigned lexicographic order, prefix smaller, is rule 3: a fixed-width
+ * value big-endian at its width with the sign bit flipped (floats: a negative value has all bits
+ * flipped, any other the sign bit set); BOOL one byte, 0 or 1; DECIMAL 16 bytes big-endian with the
+ * sign bit flipped; STRING / BINARY the payload.  Output j describes row indices[j] (indices == NULL:
+ * row j, and num_out <= nrows) by one signed 64-bit word for chunk `chunk` >= 0 of key field `field`:
+ * the bytes NK[7 chunk, 7 chunk + 7), zero-padded, big-endian in bits 63..8; the low byte 1 + the number
+ * of value bytes in the chunk (1..8), or 9 when more bytes follow the chunk; FURY_ORDER_DESC complements
+ * all 64 bits of a non-null word; a null, or a value failed under rule 6, is the minimum of the encoding
+ * (all bits 0), or the maximum (all bits 1) with FURY_ORDER_NULLS_LAST; finally the top bit is flipped,
+ * so that SIGNED int64 comparison of the words is the order.  For rows equal on all earlier chunks of
+ * this key: the signed order of the words is the order of rules 2-4; equal words whose low byte says
+ * "ended" mean equal values; "more follows" means the next chunk decides.  A chunk past the end of
+ * every value yields "ended" words with no value bytes.  *out_more (device uint32, optional) is set to
+ * 1 when any output row's value continues past the chunk, else 0.  8-byte keys take two chunks, DECIMAL
+ * three.  out_words (device, 8-byte aligned, num_out entries) is required; `flags` are the FURY_ORDER_*
+ * bits of this key.  The call is asynchronous on `stream`, never synchronises with the host and
+ * allocates no workspace.
+ * Limits: device memory only; a value is compared (or its chunk read) by one lane however long it is. */
+#define FURY_ORDER_DESC 1        /* this key position descending (nulls stay where rule 2 puts them) */
+#define FURY_ORDER_NULLS_LAST 2  /* nulls of this key position sort after every value */
+int fury_row_compare(const fury_key_side* left, const fury_key_side* right, int32_t num_keys,
+                     const int32_t* key_flags,        /* host, num_keys entries, or NULL */
+                     int64_t num_pairs,
+                     int8_t* out_cmp,                 /* device, num_pairs entries */
+                     void* stream);
+int fury_row_order_words(const fury_schema* schema, int32_t field, int32_t flags, int32_t chunk,
+                         const void* rows, const int64_t* row_offsets, int64_t nrows,
+                         const int64_t* indices,      /* device, num_out entries, or NULL */
+                         int64_t num_out,
+                         int64_t* out_words,          /* device, num_out entries */
+                         uint32_t* out_more,          /* device, one word, optional */
+                         void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
