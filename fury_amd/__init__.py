@@ -14,7 +14,8 @@ _LOOKUP = ("KeyIndex", "index_slots", "build_index_into", "build_index", "lookup
 _ORDER = ("order_flags", "compare_into", "bind_compare", "compare_rows", "order_words_into", "order_words",
           "word_continues", "refine_order", "argsort_rows", "sort_rows", "is_sorted", "search_bounds",
           "search_sorted")
-__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP, *_ORDER]
+_AGGREGATE = ("Agg", "AggResult", "aggregate_into", "bind_aggregate", "aggregate", "group_by", "group_by_rows")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP, *_ORDER, *_AGGREGATE]
 
 
 def __getattr__(name):
@@ -34,6 +35,10 @@ def __getattr__(name):
     if name in _ORDER:                            # fury_amd.order: the order of rows by key fields
         import importlib
         return getattr(importlib.import_module(".order", __name__), name)
+    if name in _AGGREGATE:                        # fury_amd.aggregate: per-group aggregates of value fields
+        import importlib                          # `from . import aggregate` would ask for "aggregate" here again
+        module = importlib.import_module(".aggregate", __name__)
+        return module if name == "aggregate" else getattr(module, name)      # the module is callable
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -61,6 +61,13 @@ class FuryKeySide(ctypes.Structure):
                 ("nrows", ctypes.c_int64), ("indices", ctypes.c_void_p)]
 
 
+class FuryAgg(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_int32), ("op", ctypes.c_int32), ("out", ctypes.c_void_p),
+                ("out_count", ctypes.c_void_p)]
+
+
+AGG_OPS = {"count": 1, "sum": 2, "min": 3, "max": 4, "argmin": 5, "argmax": 6}
+AGG_MAX_AGGS = 16
 KEYS_NULL_EQUAL = 1
 ORDER_DESC = 1
 ORDER_NULLS_LAST = 2
@@ -120,6 +127,8 @@ SIGNATURES = {
     "fury_row_compare": (ctypes.c_int, [ctypes.POINTER(FuryKeySide), ctypes.POINTER(FuryKeySide), _I32,
                                         ctypes.POINTER(_I32), _I64, _P, _P]),
     "fury_row_order_words": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "fury_row_aggregate": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, ctypes.POINTER(FuryAgg), _I32, _P]),
+    "fury_row_aggregate_lds_cells": (_I64, []),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

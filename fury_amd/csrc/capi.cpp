@@ -1474,6 +1474,106 @@ int fury_row_order_words(const fury_schema* s, int32_t field, int32_t flags, int
   return launch_checked(hs, &a, [&] { return launch_order_words(a, hs); });
 }
 
+// Per-group aggregates (aggregate.hip): BinaryRow's getters folded into one accumulator per group.
+int64_t fury_row_aggregate_lds_cells(void) { return kAggLdsCells; }
+
+int fury_row_aggregate(const fury_schema* s, const void* rows, const int64_t* row_offsets, int64_t nrows,
+                       const int64_t* group_ids, int64_t num_groups, const fury_agg* aggs, int32_t num_aggs,
+                       void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_aggregate");
+  static const char* const kOps[] = {"", "COUNT", "SUM", "MIN", "MAX", "ARGMIN", "ARGMAX"};
+  if (!s) return invalid(f, "schema is null");
+  int st = check_count(f, "nrows", nrows);
+  if (st) return st;
+  if ((st = check_required(f, "aggs", aggs))) return st;
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED, f + ": a collection schema has no row fields to aggregate");
+  if (num_aggs < 1 || num_aggs > FURY_AGG_MAX_AGGS)
+    return invalid(f, "num_aggs " + std::to_string(num_aggs) + " is not in [1, " +
+                          std::to_string(FURY_AGG_MAX_AGGS) + "]");
+  if ((st = check_count(f, "num_groups", num_groups))) return st;
+  if (num_groups > INT32_MAX) return invalid(f, "num_groups " + std::to_string(num_groups) + " > 2^31 - 1");
+  if (nrows > INT32_MAX) return invalid(f, "batch too large");
+  if (!group_ids && num_groups != 1)
+    return invalid(f, "group_ids is null: num_groups must be 1, not " + std::to_string(num_groups));
+  AggArgs a{};
+  for (int j = 0; j < num_aggs; j++) {
+    const fury_agg& g = aggs[j];
+    const std::string at = "aggs[" + std::to_string(j) + "]";
+    if (g.op < FURY_AGG_COUNT || g.op > FURY_AGG_ARGMAX)
+      return invalid(f, at + ": unknown op " + std::to_string(g.op));
+    AggRec& v = a.rec[j];
+    v.slot = g.field;
+    v.op = g.op;
+    v.kind = kFixed;
+    v.width = 8;
+    v.cls = kOrdSigned;
+    v.combine = kAggNone;
+    if (g.field == -1 && g.op == FURY_AGG_COUNT) continue;     // COUNT(*)
+    if (g.field < 0 || g.field >= s->num_fields)
+      return invalid(f, at + ": field " + std::to_string(g.field) + " is not a field of the schema");
+    if (g.op == FURY_AGG_COUNT) continue;                      // only the null bit: any type
+    const FieldPlan& p = s->plan[g.field];
+    const std::string who = at + ": " + kOps[g.op] + " of field " + std::to_string(g.field) + " (" +
+                            s->fields[g.field].name + ")";
+    const bool isfloat = p.type_id == FURY_TYPE_FLOAT32 || p.type_id == FURY_TYPE_FLOAT64;
+    const bool isint = p.type_id == FURY_TYPE_INT8 || p.type_id == FURY_TYPE_INT16 ||
+                       p.type_id == FURY_TYPE_INT32 || p.type_id == FURY_TYPE_INT64;
+    const bool word = p.kind == kFixed || p.kind == kBool;     // travels as one order word
+    const bool arg = g.op == FURY_AGG_ARGMIN || g.op == FURY_AGG_ARGMAX;
+    if (g.op == FURY_AGG_SUM && !(p.kind == kFixed && (isint || isfloat)))
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + ": SUM takes INT8 / INT16 / INT32 / INT64 / FLOAT32 / FLOAT64; DECIMAL "
+                           "sums are out of scope, a BOOL sum is the COUNT of the field under ids that drop "
+                           "the false rows");
+    if ((g.op == FURY_AGG_MIN || g.op == FURY_AGG_MAX) && !word)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + ": MIN / MAX take the fixed-width types and BOOL; for STRING / BINARY / "
+                           "DECIMAL use ARGMIN / ARGMAX, then fury_row_take at the rows whose count is not zero");
+    if (arg && !word && p.kind != kBytes && p.kind != kDecimal)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + ": a LIST / STRUCT / MAP has no order (the key types of fury_row_compare)");
+    v.kind = p.kind;
+    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+    v.cls = isfloat ? kOrdFloat : (p.kind == kBytes || p.kind == kBool) ? kOrdBytes : kOrdSigned;
+    if (g.op == FURY_AGG_SUM) {
+      v.combine = isfloat ? kAggAddFloat : kAggAddInt;
+    } else if (!word) {
+      v.combine = kAggArgVar;
+    } else {
+      v.combine = (g.op == FURY_AGG_MIN || g.op == FURY_AGG_ARGMIN) ? kAggMin : kAggMax;
+      v.resolve = arg;
+    }
+  }
+  std::vector<const void*> outs;
+  for (int j = 0; j < num_aggs; j++) {
+    const std::string at = "aggs[" + std::to_string(j) + "]";
+    if (!aggs[j].out) return invalid(f, at + ".out is null");
+    if ((st = check_aligned(f + ": " + at, 8, {{"out", aggs[j].out}, {"out_count", aggs[j].out_count}}))) return st;
+    for (const void* p : {static_cast<const void*>(aggs[j].out), static_cast<const void*>(aggs[j].out_count)}) {
+      if (!p) continue;
+      for (const void* q : outs)
+        if (p == q) return invalid(f, at + ": two outputs of one call are the same pointer");
+      outs.push_back(p);
+    }
+    a.rec[j].out = static_cast<uint64_t*>(aggs[j].out);
+    a.rec[j].out_count = aggs[j].out_count;
+  }
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"group_ids", group_ids}}))) return st;
+  if ((st = check_source(f, rows, row_offsets, nrows > 0 ? rows_of(s) : kFixedRows, nrows > 0 && num_groups > 0,
+                         &a.side)))
+    return st;
+  if (num_groups == 0) return FURY_OK;
+  a.side.nrows = nrows;
+  a.side.bitmap_bytes = s->bitmap_bytes;
+  a.side.fixed_size = s->fixed_size;
+  a.group_ids = group_ids;
+  a.num_groups = num_groups;
+  a.naggs = num_aggs;
+  return launch_checked(hs, &a, [&] { return launch_aggregate(a, hs); });
+}
+
 // The key fields of one batch, as fury_row_group and fury_row_index_build check them: the selection, then
 // no LIST / STRUCT / MAP key.  `fields` stands in for the column table check_selection wants, as in
 // fury_row_hash.

@@ -575,6 +575,53 @@ struct OrderWordsArgs {
 };
 int launch_order_words(const OrderWordsArgs& a, hipStream_t stream);
 
+// ---- per-group aggregates of value fields: aggregate.hip ----------------------------------------------------
+// Row i of `side` (side.indices unused) belongs to group group_ids[i] (NULL: group 0); ids outside
+// [0, num_groups) take part in nothing.  For aggregate j, out[g] / out_count[g] as the rules numbered in
+// include/fury_row.h define them; every entry of every given output is written once.  Bounds = "Decode
+// bounds" above: a row that fails row_ok takes part in nothing, a STRING / BINARY / DECIMAL value of an
+// ARG aggregate that fails span_ok is null for it, both raise kErrBounds with the row.  Asynchronous on
+// `stream`; workspace: 3 words per group and aggregate.
+constexpr int kMaxAggs = 16;          // FURY_AGG_MAX_AGGS
+// How an aggregate folds a value into its accumulator word.
+enum AggCombine : int32_t {
+  kAggNone = 0,                       // COUNT: only the count word
+  kAggAddInt = 1,                     // SUM of integers: 64-bit add
+  kAggAddFloat = 2,                   // SUM of floats: double add
+  kAggMin = 3,                        // MIN, ARGMIN of kFixed / kBool: unsigned min of order_fixed words
+  kAggMax = 4,                        // MAX, ARGMAX of kFixed / kBool
+  kAggArgVar = 5                      // ARGMIN / ARGMAX of kBytes / kDecimal: compare-and-swap of a row number
+};
+// One aggregate.  Indexed wave-uniformly (scalar loads): every member >= 4 bytes, see FixedCol.
+struct AggRec {
+  int32_t slot;                       // field index in the schema, -1: COUNT(*)
+  int32_t op;                         // FURY_AGG_*
+  int32_t kind;                       // FieldKind (kFixed where only the null bit is looked at)
+  int32_t width;                      // kFixed: 1 / 2 / 4 / 8; kBool: 1; kDecimal: 16
+  int32_t cls;                        // OrderClass
+  int32_t combine;                    // AggCombine
+  int32_t resolve;                    // ARGMIN / ARGMAX through kAggMin / kAggMax: the row-number pass
+  int32_t pad_;
+  uint64_t* out;
+  int64_t* out_count;
+};
+struct AggArgs {
+  KeySide side;
+  AggRec rec[kMaxAggs];
+  const int64_t* group_ids;
+  int64_t num_groups;
+  uint64_t* ws;                       // set by the launcher: [naggs][num_groups] accumulators, counts, rows
+  int32_t naggs;
+  int32_t pad_;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(AggArgs) <= 4096, "AggArgs must fit the kernel argument block");
+// The path launch_aggregate takes: groups x aggregates up to kAggLdsCells are combined per workgroup in
+// LDS (16 bytes per cell), more go to global atomics after the wave-level combine.
+constexpr int64_t kAggLdsCells = 2048;
+inline bool aggregate_uses_lds(int64_t num_groups, int naggs) { return num_groups * naggs <= kAggLdsCells; }
+int launch_aggregate(const AggArgs& a, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

@@ -4,7 +4,8 @@
 // the check of a lane's own keys that the two table kernels make first.  One implementation of rule 2 of fury_row_keys_equal: header
 // words in flight, slot_count, same_bytes and the tail rule.  Design notes: keys_equal.hip.
 // Below it the order of two rows' key fields (compare.hip) and the pieces order.hip shares with it: one
-// implementation of rules 1-4 of fury_row_compare, pair_keys_compare beside pair_keys_equal.
+// implementation of rules 1-4 of fury_row_compare, pair_keys_compare beside pair_keys_equal; its
+// value-against-value step, value_compare, is also the order of aggregate.hip's ARGMIN / ARGMAX.
 #pragma once
 
 #include "project_dev.h"
@@ -236,6 +237,31 @@ __device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_
   return nl < nr ? -1 : nl > nr ? 1 : 0;
 }
 
+// Rule 3 of fury_row_compare, ascending, for one pair of non-null values whose spans lie inside their
+// batches: -1 / 0 / +1 of the value of pr[0] (slot word s0, n0 payload bytes) against that of pr[1].
+// Shared by pair_keys_compare and the ARGMIN / ARGMAX of aggregate.hip.
+template <bool VAR>
+__device__ __forceinline__ int value_compare(int kind, int width, int cls, const PairRow (&pr)[2], uint64_t s0,
+                                             uint64_t s1, int64_t n0, int64_t n1) {
+  if (VAR && kind == kBytes)
+    return order_bytes(pr[0].rows, pr[0].base + static_cast<int32_t>(s0 >> 32), pr[0].total, n0,
+                       pr[1].rows, pr[1].base + static_cast<int32_t>(s1 >> 32), pr[1].total, n1);
+  if (VAR && kind == kDecimal) {                  // 16 bytes, little-endian two's complement
+    const int64_t pl = pr[0].base + static_cast<int32_t>(s0 >> 32);
+    const int64_t pq = pr[1].base + static_cast<int32_t>(s1 >> 32);
+    const bool al = ((pl | pq) & 7) == 0;
+    const uint64_t lo0 = pay_word(pr[0].rows, pl, pr[0].total, al);
+    const uint64_t hi0 = pay_word(pr[0].rows, pl + 8, pr[0].total, al);
+    const uint64_t lo1 = pay_word(pr[1].rows, pq, pr[1].total, al);
+    const uint64_t hi1 = pay_word(pr[1].rows, pq + 8, pr[1].total, al);
+    const uint64_t h0 = hi0 ^ (uint64_t(1) << 63), h1 = hi1 ^ (uint64_t(1) << 63);
+    return h0 != h1 ? (h0 < h1 ? -1 : 1) : lo0 < lo1 ? -1 : lo0 > lo1 ? 1 : 0;
+  }
+  if (kind == kBool) return static_cast<int>((s0 & 0xff) != 0) - static_cast<int>((s1 & 0xff) != 0);
+  const uint64_t x = order_fixed(s0, width, cls), y = order_fixed(s1, width, cls);    // kFixed
+  return x < y ? -1 : x > y ? 1 : 0;
+}
+
 // The order of the pair pr[0] / pr[1] over the key positions (key[k].left_slot of pr[0] against
 // key[k].right_slot of pr[1]): -1 / 0 / +1, the first position that differs decides.  As in
 // pair_keys_equal every key is examined for its null bit and bounds whatever the earlier keys gave,
@@ -285,29 +311,11 @@ __device__ __forceinline__ int pair_keys_compare(const PairRow (&pr)[2], COrderK
         }
       }
       if (res != 0) continue;                     // decided: only the null bits and bounds above
-      int c3 = 0;                                 // rule 3, ascending
       if (isnull[0] || isnull[1]) {               // rule 2: absolute, DESC does not flip it
         if (isnull[0] != isnull[1]) res = (isnull[0] != ((flags & FURY_ORDER_NULLS_LAST) != 0)) ? -1 : 1;
         continue;
-      } else if (VAR && kind == kBytes) {
-        c3 = order_bytes(pr[0].rows, pr[0].base + static_cast<int32_t>(slot[u][0] >> 32), pr[0].total, n[0],
-                         pr[1].rows, pr[1].base + static_cast<int32_t>(slot[u][1] >> 32), pr[1].total, n[1]);
-      } else if (VAR && kind == kDecimal) {       // 16 bytes, little-endian two's complement
-        const int64_t pl = pr[0].base + static_cast<int32_t>(slot[u][0] >> 32);
-        const int64_t pq = pr[1].base + static_cast<int32_t>(slot[u][1] >> 32);
-        const bool al = ((pl | pq) & 7) == 0;
-        const uint64_t lo0 = pay_word(pr[0].rows, pl, pr[0].total, al);
-        const uint64_t hi0 = pay_word(pr[0].rows, pl + 8, pr[0].total, al);
-        const uint64_t lo1 = pay_word(pr[1].rows, pq, pr[1].total, al);
-        const uint64_t hi1 = pay_word(pr[1].rows, pq + 8, pr[1].total, al);
-        const uint64_t h0 = hi0 ^ (uint64_t(1) << 63), h1 = hi1 ^ (uint64_t(1) << 63);
-        c3 = h0 != h1 ? (h0 < h1 ? -1 : 1) : lo0 < lo1 ? -1 : lo0 > lo1 ? 1 : 0;
-      } else if (kind == kBool) {
-        c3 = static_cast<int>((slot[u][0] & 0xff) != 0) - static_cast<int>((slot[u][1] & 0xff) != 0);
-      } else {                                    // kFixed
-        const uint64_t x = order_fixed(slot[u][0], width, c.cls), y = order_fixed(slot[u][1], width, c.cls);
-        c3 = x < y ? -1 : x > y ? 1 : 0;
       }
+      const int c3 = value_compare<VAR>(kind, width, c.cls, pr, slot[u][0], slot[u][1], n[0], n[1]);
       res = (flags & FURY_ORDER_DESC) ? -c3 : c3;
     }
   }

@@ -753,6 +753,88 @@ int fury_row_order_words(const fury_schema* schema, int32_t field, int32_t flags
                          uint32_t* out_more,          /* device, one word, optional */
                          void* stream);
 
+/* Per-group aggregates -- the last step of a GROUP BY: COUNT / SUM / MIN / MAX of value fields, and the
+ * row that holds the smallest or largest value, for every group of a batch whose rows carry a group id
+ * (fury_row_group's out_group_ids).  The batch form of reading every row's value field with BinaryRow's
+ * getters and folding it into the accumulator of the row's group, answered from the row bytes in one
+ * pass over the row headers, with nothing decoded.  Up to FURY_AGG_MAX_AGGS aggregates share that pass.
+ * The definition is normative; but for the float sums of rule 3 every output is a pure function of the
+ * batch, the ids and the aggregates:
+ *   1. Groups.  Row i belongs to group group_ids[i] (device int64, nrows entries).  A row whose id is
+ *      outside [0, num_groups) takes part in nothing and is not an error: fury_row_partition's rule,
+ *      and how a WHERE mask is applied (give the rows that fail it the id -1).  group_ids == NULL
+ *      requires num_groups == 1 and puts every row in group 0: the aggregates of the whole batch.
+ *   2. Values and nulls.  A value is what the projected decode (fury_row_project) produces for that
+ *      field of that row.  Nulls never take part.  out_count[g] (optional) = the number of values of
+ *      group g that took part in this aggregate.  A group with no values gets out[g] = 0 for COUNT,
+ *      SUM, MIN and MAX, and -1 for ARGMIN / ARGMAX: out_count[g] == 0 is the result's null flag.
+ *      COUNT looks only at the null bit, so it accepts a field of any type, LIST / STRUCT / MAP
+ *      included; with field == -1 it counts every row of the group, COUNT(*).
+ *   3. SUM.  INT8 / INT16 / INT32 / INT64: the int64 sum of the sign-extended values with two's
+ *      complement wrap-around; exact and independent of order.  FLOAT32 / FLOAT64: a double; every
+ *      value is widened exactly and the values are added in double, in an unspecified order, so this
+ *      is the only output of the call that may differ between two runs.  Its error against the exact
+ *      sum is at most (m - 1) * 2^-52 * sum |x| for m finite values, the bound of any summation order
+ *      in double; NaN and infinities propagate as IEEE addition propagates them.  Any other type
+ *      returns FURY_ERR_UNSUPPORTED naming the route: DECIMAL sums are out of scope; a BOOL sum is the
+ *      COUNT of the field under ids that drop the false rows.
+ *   4. MIN / MAX are defined for the fixed-width types (INT8 ... INT64, FLOAT32, FLOAT64, DATE32,
+ *      TIMESTAMP) and BOOL.  The order is rule 3 of fury_row_compare, ascending: signed at the value's
+ *      width, floats by totalOrder of their bits, BOOL 0 < 1.  out[g] holds the winning value's
+ *      bytes: integers, DATE32 and TIMESTAMP sign-extended to int64; BOOL 0 / 1; FLOAT64 its 8 bytes;
+ *      FLOAT32 its 4 bytes in the low half, the high half zero.  The result is bit-exact, NaN payloads
+ *      and -0.0 included.  STRING / BINARY / DECIMAL return FURY_ERR_UNSUPPORTED naming the route:
+ *      ARGMIN / ARGMAX, then fury_row_take at the rows whose count is not zero.
+ *   5. ARGMIN / ARGMAX are defined for every key type of fury_row_compare: the fixed-width types, BOOL,
+ *      DECIMAL, STRING and BINARY, in the value order of its rule 3.  out[g] (int64) = the smallest row
+ *      number among the rows of group g whose value is the minimum (maximum) of the group.  It is
+ *      deterministic: independent of how the device schedules the rows.  It is consistent:
+ *      fury_row_compare of that row against every row of the group with a non-null value, on this
+ *      field, is <= 0 (>= 0).
+ *   6. Writes.  Every entry of every given `out` and `out_count` (num_groups entries each) is written
+ *      exactly once per call, whatever the ids contain.
+ *   7. Bounds are the "Decode bounds" as rule 5 of fury_row_group applies them.  A row whose header
+ *      leaves [0, row_offsets[nrows]) takes part in nothing.  A STRING / BINARY / DECIMAL value of an
+ *      ARGMIN / ARGMAX aggregate whose span leaves the batch, or whose size is negative, counts as
+ *      null for that aggregate.  Either raises FURY_ERR_OUT_OF_BOUNDS on `stream`
+ *      (fury_device_status) naming the row.  Nothing outside the batch is read, slots of fields that
+ *      no aggregate names are never looked at, and group_ids is read at [0, nrows) only.
+ *   8. Argument checks, all on the host before any device work: schema, aggs and nrows >= 0 as the
+ *      neighbours; 1 <= num_aggs <= FURY_AGG_MAX_AGGS; 0 <= num_groups <= 2^31 - 1; nrows <= 2^31 - 1
+ *      ("batch too large"); every op one of FURY_AGG_*; every field a field of the schema (-1 only
+ *      with FURY_AGG_COUNT); the types of rules 3-5; every `out` given; `rows`, row_offsets, group_ids
+ *      and every out / out_count 8-byte aligned; no two outputs of one call the same pointer.  A
+ *      collection schema returns FURY_ERR_UNSUPPORTED, every other failure FURY_ERR_INVALID_ARGUMENT.
+ *      One field may appear under several ops, and in several aggregates.
+ * num_groups == 0 writes nothing and returns FURY_OK.  nrows == 0 with num_groups > 0 still applies
+ * rule 6 (rows and row_offsets may then be NULL).  row_offsets is ignored and may be NULL for an
+ * is_fixed schema.  The call is asynchronous on `stream` and never synchronises with the host.
+ * Workspace (stream-ordered, freed on `stream`): 24 bytes per group and aggregate -- an accumulator, a
+ * count and a row number -- whatever nrows is.
+ * Limits: device memory only; a STRING / BINARY value is compared by one lane however long it is. */
+#define FURY_AGG_COUNT  1   /* non-null values of `field`; field == -1: every row of the group (COUNT(*)) */
+#define FURY_AGG_SUM    2
+#define FURY_AGG_MIN    3
+#define FURY_AGG_MAX    4
+#define FURY_AGG_ARGMIN 5   /* the row that holds the smallest value */
+#define FURY_AGG_ARGMAX 6
+#define FURY_AGG_MAX_AGGS 16
+typedef struct fury_agg {
+  int32_t field;        /* top-level slot of the value field */
+  int32_t op;           /* FURY_AGG_* */
+  void* out;            /* device, num_groups 8-byte entries, required */
+  int64_t* out_count;   /* device, num_groups entries, optional: non-null values that took part */
+} fury_agg;
+int fury_row_aggregate(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
+                       int64_t nrows,
+                       const int64_t* group_ids,  /* device, nrows entries; NULL: every row is in group 0 */
+                       int64_t num_groups,
+                       const fury_agg* aggs, int32_t num_aggs, void* stream);
+/* Host, no device work: the call combines per workgroup on chip when num_groups * num_aggs is at most
+ * this many cells, and with global atomics above it.  The results are the same on both sides; tests use
+ * it to stand on both. */
+int64_t fury_row_aggregate_lds_cells(void);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
