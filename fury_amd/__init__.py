@@ -15,7 +15,9 @@ _ORDER = ("order_flags", "compare_into", "bind_compare", "compare_rows", "order_
           "word_continues", "refine_order", "argsort_rows", "sort_rows", "is_sorted", "search_bounds",
           "search_sorted")
 _AGGREGATE = ("Agg", "AggResult", "aggregate_into", "bind_aggregate", "aggregate", "group_by", "group_by_rows")
-__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP, *_ORDER, *_AGGREGATE]
+_PREDICATE = ("Term", "eq", "ne", "lt", "le", "gt", "ge", "is_null", "not_null", "starts_with", "ends_with",
+              "contains", "between", "predicate_into", "bind_predicate", "predicate_mask", "where", "count_where")
+__all__ = ["types", "hash_bytes", "hash_null", *_KEYS, *_GROUP, *_LOOKUP, *_ORDER, *_AGGREGATE, *_PREDICATE]
 
 
 def __getattr__(name):
@@ -39,6 +41,9 @@ def __getattr__(name):
         import importlib                          # `from . import aggregate` would ask for "aggregate" here again
         module = importlib.import_module(".aggregate", __name__)
         return module if name == "aggregate" else getattr(module, name)      # the module is callable
+    if name in _PREDICATE:                        # fury_amd.predicate: WHERE masks from conditions on the rows
+        import importlib
+        return getattr(importlib.import_module(".predicate", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

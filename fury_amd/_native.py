@@ -66,8 +66,19 @@ class FuryAgg(ctypes.Structure):
                 ("out_count", ctypes.c_void_p)]
 
 
+class FuryPredTerm(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_int32), ("op", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("literal", ctypes.c_void_p), ("literal_len", ctypes.c_int64)]
+
+
 AGG_OPS = {"count": 1, "sum": 2, "min": 3, "max": 4, "argmin": 5, "argmax": 6}
 AGG_MAX_AGGS = 16
+PRED_OPS = {"is_null": 1, "eq": 2, "lt": 3, "le": 4, "gt": 5, "ge": 6, "starts_with": 7, "ends_with": 8,
+            "contains": 9}
+PRED_NOT = 1
+PRED_OR = 2
+PRED_MAX_TERMS = 32
+PRED_MAX_LITERAL_BYTES = 2048
 KEYS_NULL_EQUAL = 1
 ORDER_DESC = 1
 ORDER_NULLS_LAST = 2
@@ -129,6 +140,7 @@ SIGNATURES = {
     "fury_row_order_words": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "fury_row_aggregate": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, ctypes.POINTER(FuryAgg), _I32, _P]),
     "fury_row_aggregate_lds_cells": (_I64, []),
+    "fury_row_predicate": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(FuryPredTerm), _I32, _P, _P, _P, _P]),
     "fury_schema_child": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_P)]),
     "fury_row_extract": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, _P, _P, _I64, _P, _I64, _P,
                                         _P, _P, _P, _P]),

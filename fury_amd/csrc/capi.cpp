@@ -1574,6 +1574,97 @@ int fury_row_aggregate(const fury_schema* s, const void* rows, const int64_t* ro
   return launch_checked(hs, &a, [&] { return launch_aggregate(a, hs); });
 }
 
+// WHERE masks (predicate.hip): BinaryRow's getters on every row, each value tested against a literal.
+int fury_row_predicate(const fury_schema* s, const void* rows, const int64_t* row_offsets, int64_t nrows,
+                       const fury_pred_term* terms, int32_t num_terms, const uint32_t* row_mask,
+                       uint32_t* out_mask, int64_t* out_count, void* stream) {
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const std::string f("fury_row_predicate");
+  static const char* const kOps[] = {"",   "IS_NULL", "EQ",          "LT",        "LE",
+                                     "GT", "GE",      "STARTS_WITH", "ENDS_WITH", "CONTAINS"};
+  if (!s) return invalid(f, "schema is null");
+  int st = check_count(f, "nrows", nrows);
+  if (st) return st;
+  if ((st = check_required(f, "terms", terms))) return st;
+  if (s->root != 0)
+    return set_error(FURY_ERR_UNSUPPORTED, f + ": a collection schema has no row fields to test");
+  if (num_terms < 1 || num_terms > FURY_PRED_MAX_TERMS)
+    return invalid(f, "num_terms " + std::to_string(num_terms) + " is not in [1, " +
+                          std::to_string(FURY_PRED_MAX_TERMS) + "]");
+  PredArgs a{};
+  int64_t pool_bytes = 0;
+  for (int j = 0; j < num_terms; j++) {
+    const fury_pred_term& t = terms[j];
+    const std::string at = "terms[" + std::to_string(j) + "]";
+    if (t.op < FURY_PRED_IS_NULL || t.op > FURY_PRED_CONTAINS)
+      return invalid(f, at + ": unknown op " + std::to_string(t.op));
+    if (t.flags & ~(FURY_PRED_NOT | FURY_PRED_OR))
+      return invalid(f, at + ": unknown flags " + std::to_string(t.flags));
+    if (t.reserved != 0) return invalid(f, at + ": reserved is " + std::to_string(t.reserved) + ", not 0");
+    if (j == 0 && (t.flags & FURY_PRED_OR))
+      return invalid(f, at + ": FURY_PRED_OR on the first term: there is no clause to join");
+    if (t.field < 0 || t.field >= s->num_fields)
+      return invalid(f, at + ": field " + std::to_string(t.field) + " is not a field of the schema");
+    const FieldPlan& p = s->plan[t.field];
+    const std::string who = at + ": " + kOps[t.op] + " on field " + std::to_string(t.field) + " (" +
+                            s->fields[t.field].name + ")";
+    if (p.kind == kOther || p.kind == kListFixed)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + ": a LIST / STRUCT / MAP cannot be tested from the row bytes; decode "
+                           "it with fury_row_project / fury_row_extract and test the decoded value");
+    const bool pattern = t.op >= FURY_PRED_STARTS_WITH;
+    if (pattern && p.kind != kBytes)
+      return set_error(FURY_ERR_UNSUPPORTED,
+                       f + ": " + who + ": STARTS_WITH / ENDS_WITH / CONTAINS take STRING / BINARY fields");
+    if (t.literal_len < 0) return invalid(f, at + ": literal_len < 0");
+    const int64_t need = t.op == FURY_PRED_IS_NULL ? 0
+                         : p.kind == kFixed        ? p.width
+                         : p.kind == kBool         ? 1
+                         : p.kind == kDecimal      ? 16
+                                                   : -1;
+    if (need >= 0 && t.literal_len != need)
+      return invalid(f, who + ": literal_len " + std::to_string(t.literal_len) + ", " + std::to_string(need) +
+                            (t.op == FURY_PRED_IS_NULL ? " needed: IS_NULL takes no literal"
+                                                       : " needed: the value's bytes as fury_row_project decodes them"));
+    if (t.literal_len > 0 && !t.literal) return invalid(f, at + ": literal is null, literal_len is not 0");
+    const int64_t padded = (t.literal_len + 7) & ~int64_t(7);
+    if (padded > FURY_PRED_MAX_LITERAL_BYTES - pool_bytes)
+      return invalid(f, at + ": the literals take more than " + std::to_string(FURY_PRED_MAX_LITERAL_BYTES) +
+                            " bytes (each literal_len rounded up to a multiple of 8)");
+    PredTerm& v = a.term[j];
+    v.slot = t.field;
+    v.kind = p.kind;
+    v.width = p.kind == kFixed ? p.width : p.kind == kDecimal ? 16 : 1;    // BOOL: one byte, 0 / 1
+    v.cls = (p.type_id == FURY_TYPE_FLOAT32 || p.type_id == FURY_TYPE_FLOAT64) ? kOrdFloat
+            : (p.kind == kBytes || p.kind == kBool)                            ? kOrdBytes
+                                                                               : kOrdSigned;
+    v.op = t.op;
+    v.flags = t.flags;
+    v.lit_word = static_cast<int32_t>(pool_bytes / 8);
+    v.lit_len = static_cast<int32_t>(t.literal_len);
+    pool_bytes += padded;
+  }
+  if ((st = check_required(f, "out_mask", out_mask))) return st;
+  if ((st = check_aligned(f, 4, {{"row_mask", row_mask}, {"out_mask", out_mask}}))) return st;
+  if ((st = check_aligned(f, 8, {{"row_offsets", row_offsets}, {"out_count", out_count}}))) return st;
+  if ((nrows + 255) / 256 > INT32_MAX) return invalid(f, "batch too large");
+  if ((st = check_source(f, rows, row_offsets, nrows > 0 ? rows_of(s) : kFixedRows, nrows > 0, &a.side))) return st;
+  // the literals, copied now: the pool travels in the kernel-argument block (zeros pad each to whole words)
+  for (int j = 0; j < num_terms; j++)
+    if (terms[j].literal_len > 0)
+      std::memcpy(reinterpret_cast<uint8_t*>(a.pool) + 8 * static_cast<int64_t>(a.term[j].lit_word),
+                  terms[j].literal, static_cast<size_t>(terms[j].literal_len));
+  a.side.nrows = nrows;
+  a.side.bitmap_bytes = s->bitmap_bytes;
+  a.side.fixed_size = s->fixed_size;
+  a.nterms = num_terms;
+  a.row_mask = row_mask;
+  a.out_mask = out_mask;
+  a.out_count = reinterpret_cast<unsigned long long*>(out_count);
+  if (nrows == 0 && !out_count) return FURY_OK;
+  return launch_checked(hs, &a, [&] { return launch_predicate(a, hs); });
+}
+
 // The key fields of one batch, as fury_row_group and fury_row_index_build check them: the selection, then
 // no LIST / STRUCT / MAP key.  `fields` stands in for the column table check_selection wants, as in
 // fury_row_hash.

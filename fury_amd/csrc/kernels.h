@@ -622,6 +622,41 @@ constexpr int64_t kAggLdsCells = 2048;
 inline bool aggregate_uses_lds(int64_t num_groups, int naggs) { return num_groups * naggs <= kAggLdsCells; }
 int launch_aggregate(const AggArgs& a, hipStream_t stream);
 
+// ---- WHERE masks from conditions on the rows: predicate.hip ---------------------------------------------------
+// Bit i of out_mask = row i of `side` (side.indices unused) passes the conjunction of clauses that
+// term[0 .. nterms) spell, as the rules numbered in include/fury_row.h define it; whole 32-bit words,
+// tail bits zero.  row_mask (optional, may be out_mask itself): a row whose bit is 0 is not read and
+// fails.  *out_count (optional; zeroed on the stream by the launcher) = the bits set.  Bounds = "Decode
+// bounds" above: a row that fails row_ok has every field null, a STRING / BINARY / DECIMAL value that
+// fails span_ok is null, both raise kErrBounds with the row.  Asynchronous on `stream`, no workspace.
+constexpr int kMaxPredTerms = 32;         // FURY_PRED_MAX_TERMS
+constexpr int kPredPoolWords = 256;       // FURY_PRED_MAX_LITERAL_BYTES / 8
+// One term.  Indexed wave-uniformly (scalar loads): every member >= 4 bytes, see FixedCol.
+struct PredTerm {
+  int32_t slot;                       // field index in the schema
+  int32_t kind;                       // FieldKind: kFixed / kBool / kBytes / kDecimal
+  int32_t width;                      // kFixed: 1 / 2 / 4 / 8; kBool: 1; kDecimal: 16
+  int32_t cls;                        // OrderClass
+  int32_t op;                         // FURY_PRED_*
+  int32_t flags;                      // FURY_PRED_NOT | FURY_PRED_OR
+  int32_t lit_word;                   // the literal's first word in PredArgs.pool
+  int32_t lit_len;                    // its bytes; the words hold zeros past them
+};
+struct PredArgs {
+  KeySide side;
+  PredTerm term[kMaxPredTerms];
+  uint64_t pool[kPredPoolWords];      // every literal, each padded with zeros to whole 8-byte words
+  int32_t nterms;
+  int32_t pad_;
+  const uint32_t* row_mask;
+  uint32_t* out_mask;
+  unsigned long long* out_count;
+  uint32_t* err;                      // the launch stream's device error slot or NULL
+};
+static_assert(sizeof(PredArgs) <= 4096, "PredArgs must fit the kernel argument block");
+// FURY_ERR_INVALID_ARGUMENT ("batch too large") for a row count the grid cannot index.
+int launch_predicate(const PredArgs& a, hipStream_t stream);
+
 // ---- nested values as batches: extract.hip -------------------------------------------------------
 // BinaryRow.getStruct / getArray / getMap over a batch, along a path of struct slots: the bytes each
 // row's slot points at, unchanged, packed into a new batch (compact, in row order, shaped like

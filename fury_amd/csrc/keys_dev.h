@@ -5,7 +5,8 @@
 // words in flight, slot_count, same_bytes and the tail rule.  Design notes: keys_equal.hip.
 // Below it the order of two rows' key fields (compare.hip) and the pieces order.hip shares with it: one
 // implementation of rules 1-4 of fury_row_compare, pair_keys_compare beside pair_keys_equal; its
-// value-against-value step, value_compare, is also the order of aggregate.hip's ARGMIN / ARGMAX.
+// value-against-value step, value_compare, is also the order of aggregate.hip's ARGMIN / ARGMAX, and
+// its pieces (order_fixed, order_decimal, order_spans) order a value against a literal in predicate.hip.
 #pragma once
 
 #include "project_dev.h"
@@ -207,12 +208,32 @@ __device__ __forceinline__ int order_word_cmp(uint64_t x, uint64_t y) {
   return bx < by ? -1 : bx > by ? 1 : 0;
 }
 
-// Batch bytes [pl, pl + nl) of the left batch against [pr, pr + nr) of the right one, unsigned
-// lexicographic, a proper prefix first; both spans lie inside their batches (slot_count).  The first
-// differing 8-byte word decides; the tail is masked and the lengths break a tie.
-__device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_t tl, int64_t nl,
-                                           const uint8_t* rr, int64_t pr, int64_t tr, int64_t nr) {
-  const bool al = ((pl | pr) & 7) == 0;           // every well-formed row: aligned 8-byte loads
+// A side of the bytes order: where its 8-byte words come from.  BatchBytes: a value's span inside a
+// batch (slot_count), read through pay_word / pay_tail.  LiteralBytes (predicate.hip): words in the
+// kernel-argument block, zero-padded to whole words, read through scalar loads where the index is
+// wave-uniform.
+struct BatchBytes {
+  const uint8_t* rows;
+  int64_t p;                          // absolute start of the span
+  int64_t total;                      // the batch's row bytes
+  bool al;                            // aligned 8-byte loads
+  __device__ __forceinline__ uint64_t word(int64_t w) const { return pay_word(rows, p + 8 * w, total, al); }
+  __device__ __forceinline__ uint64_t tail(int64_t w, int rem) const {
+    return pay_tail(rows, p + 8 * w, rem, total, al);
+  }
+};
+struct LiteralBytes {
+  __attribute__((address_space(4))) const uint64_t* words;
+  __device__ __forceinline__ uint64_t word(int64_t w) const { return words[w]; }
+  __device__ __forceinline__ uint64_t tail(int64_t w, int rem) const {
+    return words[w] & (~uint64_t(0) >> (64 - 8 * rem));
+  }
+};
+
+// The nl bytes of `l` against the nr bytes of `r`, unsigned lexicographic, a proper prefix first.  The
+// first differing 8-byte word decides; the tail is masked and the lengths break a tie.
+template <class L, class R>
+__device__ __forceinline__ int order_spans(const L& l, int64_t nl, const R& r, int64_t nr) {
   const int64_t n = nl < nr ? nl : nr;
   const int64_t nw = n >> 3;
   for (int64_t w0 = 0; w0 < nw; w0 += kPayWords) {
@@ -221,8 +242,8 @@ __device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_
     for (int u = 0; u < kPayWords; u++) {
       x[u] = y[u] = 0;
       if (w0 + u < nw) {
-        x[u] = pay_word(rl, pl + 8 * (w0 + u), tl, al);
-        y[u] = pay_word(rr, pr + 8 * (w0 + u), tr, al);
+        x[u] = l.word(w0 + u);
+        y[u] = r.word(w0 + u);
       }
     }
 #pragma unroll
@@ -231,10 +252,24 @@ __device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_
   }
   const int rem = static_cast<int>(n & 7);
   if (rem) {
-    const int c = order_word_cmp(pay_tail(rl, pl + 8 * nw, rem, tl, al), pay_tail(rr, pr + 8 * nw, rem, tr, al));
+    const int c = order_word_cmp(l.tail(nw, rem), r.tail(nw, rem));
     if (c) return c;
   }
   return nl < nr ? -1 : nl > nr ? 1 : 0;
+}
+
+// Batch bytes [pl, pl + nl) of the left batch against [pr, pr + nr) of the right one; both spans lie
+// inside their batches (slot_count).
+__device__ __forceinline__ int order_bytes(const uint8_t* rl, int64_t pl, int64_t tl, int64_t nl,
+                                           const uint8_t* rr, int64_t pr, int64_t tr, int64_t nr) {
+  const bool al = ((pl | pr) & 7) == 0;           // every well-formed row: aligned 8-byte loads
+  return order_spans(BatchBytes{rl, pl, tl, al}, nl, BatchBytes{rr, pr, tr, al}, nr);
+}
+
+// Two DECIMAL values, 16 bytes little-endian two's complement each, as (low word, high word).
+__device__ __forceinline__ int order_decimal(uint64_t lo0, uint64_t hi0, uint64_t lo1, uint64_t hi1) {
+  const uint64_t h0 = hi0 ^ (uint64_t(1) << 63), h1 = hi1 ^ (uint64_t(1) << 63);
+  return h0 != h1 ? (h0 < h1 ? -1 : 1) : lo0 < lo1 ? -1 : lo0 > lo1 ? 1 : 0;
 }
 
 // Rule 3 of fury_row_compare, ascending, for one pair of non-null values whose spans lie inside their
@@ -254,8 +289,7 @@ __device__ __forceinline__ int value_compare(int kind, int width, int cls, const
     const uint64_t hi0 = pay_word(pr[0].rows, pl + 8, pr[0].total, al);
     const uint64_t lo1 = pay_word(pr[1].rows, pq, pr[1].total, al);
     const uint64_t hi1 = pay_word(pr[1].rows, pq + 8, pr[1].total, al);
-    const uint64_t h0 = hi0 ^ (uint64_t(1) << 63), h1 = hi1 ^ (uint64_t(1) << 63);
-    return h0 != h1 ? (h0 < h1 ? -1 : 1) : lo0 < lo1 ? -1 : lo0 > lo1 ? 1 : 0;
+    return order_decimal(lo0, hi0, lo1, hi1);
   }
   if (kind == kBool) return static_cast<int>((s0 & 0xff) != 0) - static_cast<int>((s1 & 0xff) != 0);
   const uint64_t x = order_fixed(s0, width, cls), y = order_fixed(s1, width, cls);    // kFixed

@@ -835,6 +835,106 @@ int fury_row_aggregate(const fury_schema* schema, const void* rows, const int64_
  * it to stand on both. */
 int64_t fury_row_aggregate_lds_cells(void);
 
+/* WHERE masks -- which rows of a batch pass a condition on their fields?  The batch form of reading the
+ * named fields of every row with BinaryRow's getters and testing each value against a literal, answered
+ * from the row bytes with nothing decoded: one bit per row, in the shape fury_row_filter,
+ * fury_row_update and the other mask consumers read.  Up to FURY_PRED_MAX_TERMS tests share one pass
+ * over the row headers.  The reference ships no predicate over rows; the definition below is this
+ * library's and is normative, so that a worker in any language selects the rows the device does:
+ *   1. Shape.  The terms form a conjunction of clauses.  Term t starts a new clause unless it carries
+ *      FURY_PRED_OR; with FURY_PRED_OR it is OR-ed into the clause of term t - 1 (term 0 with
+ *      FURY_PRED_OR is an argument error).  A row passes when every clause has at least one true term.
+ *      BETWEEN is two clauses; a short IN list is EQ terms OR-ed together; a long IN list is a
+ *      fury_row_lookup against the list, whose out_mask is chained in through row_mask.
+ *   2. Fields and literals.  The supported fields are the key types of fury_row_keys_equal: the
+ *      fixed-width types (INT8 / INT16 / INT32 / INT64 / FLOAT32 / FLOAT64 / DATE32 / TIMESTAMP), BOOL,
+ *      DECIMAL, STRING and BINARY.  A LIST / STRUCT / MAP field returns FURY_ERR_UNSUPPORTED, under
+ *      every op, naming the route: fury_row_project / fury_row_extract, then a test on the decoded
+ *      value.  The literal is the value's bytes as the projected decode (fury_row_project) would produce
+ *      them: a fixed-width type exactly `width` little-endian bytes; BOOL 1 byte, non-zero = true;
+ *      DECIMAL 16 bytes, little-endian two's complement; STRING / BINARY any length, 0 included.  A
+ *      wrong literal_len for a fixed-size type is an argument error.  The literal is HOST memory and
+ *      is copied during the call.  FURY_PRED_IS_NULL takes no literal (literal_len 0).
+ *   3. Comparison ops.  FURY_PRED_EQ / LT / LE / GT / GE are true exactly where fury_row_compare
+ *      (ascending; rules 3 and 5 there) of the row's value against a value with the literal's bytes
+ *      gives 0 / -1 / <= 0 / +1 / >= 0.  Floats therefore compare by totalOrder of their bits: EQ 0.0
+ *      does not match -0.0, EQ of a NaN matches the NaNs with the same bits, and a positive NaN is GT
+ *      every number.  Strings compare by unsigned bytes, a proper prefix smaller.  The consequence: a
+ *      range predicate selects exactly the rows that fury_row_compare's binary search (search_sorted)
+ *      delimits in the batch sorted by that field.
+ *   4. Pattern ops, STRING / BINARY only, byte-wise on the payload (no code points, no case folding).
+ *      FURY_PRED_STARTS_WITH / FURY_PRED_ENDS_WITH: the value has at least literal_len bytes and its
+ *      first / last literal_len bytes equal the literal.  FURY_PRED_CONTAINS: the literal occurs at
+ *      some byte offset of the value.  An empty literal matches every non-null value.  A pattern op on
+ *      any other field returns FURY_ERR_UNSUPPORTED.
+ *   5. Nulls.  FURY_PRED_IS_NULL is true where the field's null bit is set; with FURY_PRED_NOT it is
+ *      true where the bit is clear.  Every other term on a null value is not true, with or without
+ *      FURY_PRED_NOT: FURY_PRED_NOT makes a term true where its test is false and the value is not
+ *      null.  Negation exists only on terms and a row must be TRUE to pass, so this is exactly SQL's
+ *      three-valued WHERE: a comparison with NULL is UNKNOWN, NOT UNKNOWN is UNKNOWN, and UNKNOWN
+ *      does not pass.
+ *   6. Outputs.  Bit i of out_mask, LSB-first in 32-bit words (word i / 32, bit i % 32: the shape
+ *      fury_row_filter reads), is 1 when row i passes.  Every word in [0, (nrows + 31) / 32) is
+ *      written, bits at or past nrows are 0, and nothing past the last word is written.  *out_count,
+ *      when given, receives the exact number of set bits.  row_mask, when given, is read in the same
+ *      format: a row whose bit is 0 is not read at all and fails.  row_mask == out_mask, the identical
+ *      pointer, is allowed and refines a mask in place; any other overlap gives unspecified contents.
+ *      nrows == 0 writes *out_count = 0 and touches nothing else.
+ *   7. Bounds are rule 6 of fury_row_compare applied to one side.  A row whose header leaves
+ *      [0, row_offsets[nrows]) has every field null; a STRING / BINARY / DECIMAL value whose span
+ *      leaves the batch, or whose size is negative, is null.  Each such failure raises
+ *      FURY_ERR_OUT_OF_BOUNDS on `stream` (fury_device_status) naming the row; the mask is still
+ *      defined, by rules 1-5 with those nulls.  Every term's null bit and span are examined whatever
+ *      the earlier terms gave, so the reported error does not depend on short-circuiting.  Nothing
+ *      outside the batch is read -- this includes the 1-7 bytes that follow the batch's last value --
+ *      and slots of fields that no term names are never looked at.
+ *   8. Argument checks, all on the host before any device work, every message starting with
+ *      fury_row_predicate: schema, terms and out_mask given, nrows >= 0; 1 <= num_terms <=
+ *      FURY_PRED_MAX_TERMS; every op one of FURY_PRED_*; no flag bits but FURY_PRED_NOT and
+ *      FURY_PRED_OR, no FURY_PRED_OR on term 0; `reserved` 0; every field a field of the schema, of a
+ *      type rules 2 and 4 accept; literal_len >= 0, the length rule 2 fixes, 0 for FURY_PRED_IS_NULL;
+ *      `literal` not NULL where literal_len > 0; the literal pool -- the sum over the terms of
+ *      literal_len rounded up to a multiple of 8 -- at most FURY_PRED_MAX_LITERAL_BYTES; `rows`,
+ *      row_offsets and out_count 8-byte aligned, row_mask and out_mask 4-byte aligned; nrows small
+ *      enough for one launch ("batch too large" past 2^39 - 256).  A collection schema and the type
+ *      failures return FURY_ERR_UNSUPPORTED, every other failure FURY_ERR_INVALID_ARGUMENT.  One field
+ *      may appear in several terms.  row_offsets is ignored and may be NULL for an is_fixed schema, as
+ *      elsewhere.
+ * The call is asynchronous on `stream`, never synchronises with the host and allocates no workspace
+ * (out_count is zeroed by a memset on the stream); it is safe to bind and re-issue.
+ * Limits: device memory only; a STRING / BINARY value is compared or scanned by one lane however long
+ * it is.  FURY_PRED_CONTAINS is the plain search: one comparison of up to 8 bytes per byte offset of
+ * the value, and at every offset where the literal's first 8 bytes match, a comparison of the rest of
+ * the literal, so its worst case (a repetitive literal of m bytes in a repetitive value of n bytes) is
+ * n * m / 8 word comparisons and loads in one lane. */
+#define FURY_PRED_IS_NULL      1   /* no literal */
+#define FURY_PRED_EQ           2
+#define FURY_PRED_LT           3
+#define FURY_PRED_LE           4
+#define FURY_PRED_GT           5
+#define FURY_PRED_GE           6
+#define FURY_PRED_STARTS_WITH  7   /* STRING / BINARY only */
+#define FURY_PRED_ENDS_WITH    8
+#define FURY_PRED_CONTAINS     9
+#define FURY_PRED_NOT 1            /* flags: the term is true where the test is false (value non-null) */
+#define FURY_PRED_OR  2            /* flags: this term joins the clause of the term before it */
+#define FURY_PRED_MAX_TERMS 32
+#define FURY_PRED_MAX_LITERAL_BYTES 2048   /* sum over terms of literal_len rounded up to 8 */
+typedef struct fury_pred_term {
+  int32_t field;            /* top-level slot of the field */
+  int32_t op;               /* FURY_PRED_* */
+  int32_t flags;            /* FURY_PRED_NOT | FURY_PRED_OR */
+  int32_t reserved;         /* must be 0 */
+  const void* literal;      /* HOST memory, copied during the call; NULL for FURY_PRED_IS_NULL */
+  int64_t literal_len;
+} fury_pred_term;           /* 32 bytes */
+int fury_row_predicate(const fury_schema* schema, const void* rows, const int64_t* row_offsets,
+                       int64_t nrows, const fury_pred_term* terms, int32_t num_terms,
+                       const uint32_t* row_mask,   /* device, optional: rows to examine */
+                       uint32_t* out_mask,         /* device, (nrows + 31) / 32 words, required */
+                       int64_t* out_count,         /* device, optional: number of bits set */
+                       void* stream);
+
 /* Nested values as batches -- BinaryRow.getStruct / getArray / getMap (ordinal) over a batch
  * (FMT/row/binary/UnsafeTrait.java:160-197; BinaryMap.pointTo, FMT/row/binary/BinaryMap.java:62-77):
  * one bitmap bit, one 8-byte slot and a pointTo(buffer, baseOffset + relativeOffset, size).  A nested
